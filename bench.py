@@ -1,7 +1,11 @@
 """Benchmark: alpha-mattes/sec of unet.UNetVideo at 1920x1080 (BASELINE.json configs[1]; configs[3] at N>1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|fp32] [--dump-outputs DIR] [--full]
     python bench.py --gpus N --dist-selftest      # CPU-only (gloo) check of the N-rank launcher and collectives
+
+A plain run sets up, warms up, times the K steps and prints the headline line; --dump-outputs DIR also writes the
+last timed step's alpha mattes (DIR/alpha.npy, float32: same arguments, same inputs, so two builds compare output
+for output).  --full adds every other measurement below (roofline pass, sub-records, parity, CPU baselines).
 
 With --gpus N > 1 bench.py starts its own N ranks (one child process per GPU, RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_ADDR=127.0.0.1 / MASTER_PORT in their environment) before anything touches a GPU, waits for them and exits
@@ -13,7 +17,7 @@ in HBM before timing).  Frame-parallel: every rank runs its own frames, no colle
 path (scaling "weak"); the packed weights are RCCL-broadcast from rank 0 once, before timing.
 Rank 0 prints ONE JSON line (value = frames processed by all ranks / max-over-ranks time).
 
-Sub-records on the same line: video_batch (config 4: 256 frames sharded + all-gathered), temporal
+Sub-records on the same line with --full: video_batch (config 4: 256 frames sharded + all-gathered), temporal
 (config 3: warp + occlusion + refine), fp32 (the path that meets north_star's 1e-4 bound), parity
 (bf16 vs fp32 vs the CPU oracle on the timed frame), train (config 5), loader and augment.
 """
@@ -1287,6 +1291,22 @@ def dist_selftest(rank, world):
 
 # ------------------------------------------------------------------------------------------------ main
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, name, t, world=1):
+    """--dump-outputs: the device tensor `t` as path/name.npy in float32.  The ranks share 64 MB; an output past a
+    rank's share is written as a fixed sample instead: the elements at sorted flat indices drawn without replacement
+    from RandomState(0), the same for every run of the same shape."""
+    os.makedirs(path, exist_ok=True)
+    a = t.detach().to(torch.float32).cpu().numpy()
+    keep = (DUMP_MAX_BYTES - 4096 * world) // 4 // world  # room for the .npy headers
+    if a.size > keep:
+        idx = np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))
+        a = a.reshape(-1)[idx]
+    np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1296,10 +1316,17 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop also run everything else this benchmark measures: the per-conv "
+                         "roofline pass, the config-3/4/5, loader and augment records, the fp32 / split-operand "
+                         "forwards, parity and the CPU baselines (each can be dropped again by its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's output (the alpha mattes a caller of the timed "
+                         "forward receives) as DIR/alpha.npy, float32; N > 1: DIR/alpha_rank<r>.npy per rank")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=3, help="full 1080p frames timed for the CPU baseline (median)")
-    ap.add_argument("--no-profile", action="store_true", help="skip per-conv HIP events")
-    ap.add_argument("--layers", action="store_true", help="per-conv timing breakdown on stderr")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip per-conv HIP events")
+    ap.add_argument("--layers", action="store_true", help="--full: per-conv timing breakdown on stderr")
     ap.add_argument("--no-graph", action="store_true", help="time eager launches instead of the captured HIP graph")
     ap.add_argument("--no-up-head", action="store_true",
                     help="upconv_4 stores its output and the head reads it (A/B of the fused up-head)")
@@ -1444,6 +1471,35 @@ def main():
     elapsed = time.perf_counter() - t0
     alpha_timed = (graphed.output if graphed is not None else model.output).clone()
     logits_timed = model.conv1_3.clone()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "alpha" if world == 1 else "alpha_rank%d" % rank, alpha_timed, world)
+
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    frames = world * B * args.steps
+    value = frames / elapsed
+    ms_step = 1000.0 * elapsed / args.steps
+    rec = {"metric": METRIC, "value": round(value, 3), "unit": "frames/s", "n_gpus": world,
+           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+           "data": "synthetic (seeded 1080p cmp/bg/trimap frames; synthetic VGG16 + init_conv weights)",
+           "config": {"workload": "unet.UNetVideo forward (20 3x3 convs, 3.233 TFLOP/frame), %dx%d 7-ch NHWC"
+                                  % (W, H),
+                      "frames_per_step_per_gpu": B, "height": H, "width": W,
+                      "launch": "eager" if args.no_graph else "hip-graph replay",
+                      "parallelism": "frame-parallel dp%d" % world},
+           "achieved_tflops_whole_forward": round(value / world * flops_per_frame / 1e12, 2),
+           "roofline": None, "cpu_baseline": None}
+    if not args.full:  # the plain run: the headline figure alone
+        if args.layers:
+            log("bench: --layers is part of the --full run; nothing per conv was timed")
+        if rank == 0:
+            print(json.dumps(rec), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
 
     # per-kernel HIP events cost ~10% of the step (a marker between every launch), so the roofline pass is a
     # second, identical K-step pass with an event pair on the launch stream around every conv
@@ -1454,14 +1510,6 @@ def main():
             model.forward(x)
         torch.cuda.synchronize()
         ops.conv_profile(False)
-
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    frames = world * B * args.steps
-    value = frames / elapsed
-    ms_step = 1000.0 * elapsed / args.steps
 
     vrec = None
     if args.video_frames > 0:
@@ -1497,17 +1545,7 @@ def main():
 
     roofline = conv_roofline(prof, args) if prof else None
     if rank == 0:
-        rec = {"metric": METRIC, "value": round(value, 3), "unit": "frames/s", "n_gpus": world,
-               "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
-               "data": "synthetic (seeded 1080p cmp/bg/trimap frames; synthetic VGG16 + init_conv weights)",
-               "config": {"workload": "unet.UNetVideo forward (20 3x3 convs, 3.233 TFLOP/frame), %dx%d 7-ch NHWC"
-                                      % (W, H),
-                          "frames_per_step_per_gpu": B, "height": H, "width": W,
-                          "launch": "eager" if args.no_graph else "hip-graph replay",
-                          "parallelism": "frame-parallel dp%d" % world},
-               "achieved_tflops_whole_forward": round(value / world * flops_per_frame / 1e12, 2),
-               "roofline": roofline, "cpu_baseline": None}
+        rec["roofline"] = roofline
         src, tr = load_profile("traffic", args)
         if tr and tr.get("bytes_per_forward"):
             # whole-forward HBM traffic (PMC FETCH_SIZE x2 + WRITE_SIZE summed over every kernel of one forward,

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 KEY=$1; shift
-FWD="--no-cpu-baseline --no-train --no-loader --no-augment --no-temporal --no-fp32 --video-frames 0 --steps ${SW_STEPS:-200} --warmup 10"
+FWD="--full --no-cpu-baseline --no-train --no-loader --no-augment --no-temporal --no-fp32 --video-frames 0 --steps ${SW_STEPS:-200} --warmup 10"
 for i in ${SW_ROUNDS:-1 2}; do
   for v in "$@"; do
     L=gpurun_out/sweep_${KEY}_${v}_$i.log

@@ -4,6 +4,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=${1:-quick}
+BENCH_ARGS="--full ${BENCH_ARGS}"  # --layers is part of the full run
 if [ -z "$NO_TESTS" ]; then
   timeout -k 10 900 python -m pytest tests -q -m "gpu and not slow" -x -rf > gpurun_out/pytest_gpu.log 2>&1
   rc=$?; tail -n 3 gpurun_out/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc

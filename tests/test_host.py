@@ -259,6 +259,27 @@ def test_bench_refuses_a_world_other_than_gpus():
     assert "initialised world" in err
 
 
+def test_bench_dump_outputs_writes_float32_and_samples_past_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an output within the cap is written whole as float32 (bf16 in, exact widening); one
+    past the cap as a fixed sample — sorted distinct flat indices, the same on every call — within the cap on disk."""
+    import torch
+    from conftest import REPO
+    monkeypatch.syspath_prepend(REPO)
+    import bench
+    t = (torch.arange(2 * 5 * 7, dtype=torch.float32).reshape(2, 5, 7, 1) / 8).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "a"), "alpha", t)
+    got = np.load(tmp_path / "a" / "alpha.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 5, 7, 1) and np.array_equal(got, t.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 4096 + 40 * 4)  # two ranks: 20 elements each
+    big = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), "alpha_rank1", big, world=2)
+    s1, s2 = (np.load(tmp_path / d / "alpha_rank1.npy") for d in ("b", "c"))
+    assert s1.dtype == np.float32 and s1.shape == (20,) and np.array_equal(s1, s2)
+    assert (np.diff(s1) > 0).all() and 0 <= s1[0] and s1[-1] < 1000  # values = their own indices: sorted, distinct
+    assert 2 * os.path.getsize(tmp_path / "b" / "alpha_rank1.npy") <= bench.DUMP_MAX_BYTES
+
+
 @pytest.mark.parametrize("h,w,n,fact", [(1080, 1920, 5, 0.05), (37, 51, 5, 0.05), (64, 64, 4, 0.1), (9, 300, 6, 0.2)])
 def test_deform_grid_draws_match_the_reference_loop(h, w, n, fact):
     """tps.deform_grid draws its landmark offsets as one array; the reference (tps.py:127-143, restated in

@@ -28,7 +28,7 @@ run() {  # run <limit> <log> cmd...
 skip() { [[ " $SKIP " == *" $1 "* ]]; }
 if ! skip fwd; then
 run 300 stats.log rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run \
-    -- python3 "$REPO/bench.py" --steps 50 --warmup 5 $FWD "$@"
+    -- python3 "$REPO/bench.py" --full --steps 50 --warmup 5 $FWD "$@"
 cp "$(find "$OUT/stats" -name '*kernel_stats.csv' | head -n 1)" "$REPO/profiles/${TAG}_kernel_stats.csv"
 grep "^{\"metric\"" "$OUT/stats.log" | tail -n 1 > "$REPO/profiles/${TAG}_stats_bench.json"
 fi
@@ -88,6 +88,6 @@ for sp in x3:f16x3 x6:bf16x6; do
 done
 cp "$REPO"/profiles/${TAG}_* "$REPO/gpurun_out/"
 skip bench && exit 0
-run 600 bench.log python3 "$REPO/bench.py" --layers "$@"
+run 600 bench.log python3 "$REPO/bench.py" --full --layers "$@"
 tail -n 1 "$OUT/bench.log" > "$REPO/gpurun_out/${TAG}_bench.json"
 grep -E "conv #|launches" "$OUT/bench.log" > "$REPO/gpurun_out/${TAG}_bench_layers.log" || true
