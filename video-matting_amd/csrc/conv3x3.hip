@@ -12,7 +12,9 @@
 //   channel-chunk-major — granule g covers channels (g/9)*GE .. +GE of tap g%9 — so the 9 taps that
 //   re-read the same input rows are consecutive K-steps and hit L2; otherwise tap-major k = tap*cin_pad+c.
 //
-// Two kernels:
+// This file: routing, the C entry points, the option table (vm_set_option), and every kernel family but the
+// row-stationary one (conv_rows.hip) and the strip pair (conv_pair.hip), each under its own heading.  The two generic
+// kernels:
 //   conv3x3_mfma  register-staged, 256 threads, tiles 128x128 / 256x64, 128-byte K-steps, 2-slot LDS.
 //                 Used for small grids, the fused softmax and as the reference implementation.
 //   conv3x3_glds  LDS-DMA pipelined (buffer_load ... lds), 512 threads, tiles 256x256 / 256x128 / 512x64,
@@ -24,7 +26,9 @@
 #include <type_traits>
 #include <cstdio>
 
-#include "conv_common.h"
+#include <initializer_list>
+
+#include "conv_dispatch.h"
 
 namespace vm {
 
@@ -4752,6 +4756,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // name of the kernel the last conv call on this thread launched, spelled as rocprofv3 reports it
 // (bench.py matches its per-launch PMC traffic by this name)
 thread_local char g_last_kernel[128];
+ConvOptions g_opt;
 template <typename T>
 static const char* tname() { return sizeof(T) == 2 ? "unsigned short" : "float"; }
 
@@ -4794,20 +4799,6 @@ static int launch_glds(ConvArgs& a, hipStream_t st) {
   return check_launch("conv3x3_glds");
 }
 
-static long g_border_ks = 1;  // folded-upconv border pass: granule split (1, 2 or 4 wave groups per block)
-static long g_up_skip_mask = 3;  // folded upconvs: which zero taps are skipped (1 = kernel row, 2 = column, 3 = both)
-static long g_patch_repi = 1;  // patch kernel: register epilogue (bf16 outputs, no packed frames) where the tiling allows
-// channel-banded patch tiles (ConvArgs::cband): 0 off, 1 folded upconvs, 2 all.  Off: measured on upconv_2 (9.4 MB
-// folded filter) 0.261 -> 0.312 ms and on the L5 convs 0.053 -> 0.057 ms (same box, bench.py --option cband=0|1|2):
-// every XCD then reads the whole input from the Infinity Cache, which costs more than the weight stream it saves
-static long g_cband = 0;
-static long g_cband_bytes = 4L << 20;   // ... for filters of at least this many bytes (an XCD's L2)
-// grouped tile order (ConvArgs::ngroup): this many output tiles per group for filters of >= cband_bytes (0: off) —
-// the XCD working set is ngroup filter slices instead of the whole filter; the input is read tiles_n / ngroup times.
-// Off: same-box A/B (gpurun_out/r6g_ab.log, profiles/r06g_ngroup_ab.log) bf16 forward 2.967 -> 2.993..3.010 ms for
-// ngroup 2..8, f16x3 10.04 -> 10.01..10.04 ms: the re-streamed filter slices come from the Infinity Cache
-static long g_ngroup = 0;
-
 template <int BN, int WM, int WN, int S, int TH = 8, int MINB = 1, int UNR = 9, bool PF = false, int ABL = 0,
           bool FIRST = false, int G = 1, bool UPSKIP = false>
 static int launch_patch(ConvArgs& a, hipStream_t st) {
@@ -4832,18 +4823,18 @@ static int launch_patch(ConvArgs& a, hipStream_t st) {
   const long sp = a.vstride ? ((a.H + C::TH - 1) / C::TH) * (long)((a.vW + C::TW - 1) / C::TW)
                             : N * ((a.H + C::TH - 1) / C::TH) * ((a.W + C::TW - 1) / C::TW);
   a.tiles_n = (a.cout + BN - 1) / BN;
-  a.repi = (int)g_patch_repi;
-  a.upmask = (int)g_up_skip_mask;
-  a.prio = (int)g_conv_prio;
+  a.repi = (int)g_opt.patch_repi;
+  a.upmask = (int)g_opt.up_skip_mask;
+  a.prio = (int)g_opt.conv_prio;
   if (sp * a.tiles_n > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3: too many tiles");
   a.tiles_total = (int)(sp * a.tiles_n);
   // channel-banded tile order (ConvArgs::cband) for weight-heavy layers: the whole filter exceeds an XCD's 4 MB L2
   // and its output tiles split evenly over the 8 XCDs.  cband option: 0 off, 1 folded upconvs, 2 any such layer
   const long wbytes = (long)a.cout_pad * a.K_pad * 2;
-  a.cband = (g_cband >= (a.up ? 1 : 2)) && !FIRST && BN == 64 && a.tiles_n % 8 == 0 && wbytes >= g_cband_bytes
+  a.cband = (g_opt.cband >= (a.up ? 1 : 2)) && !FIRST && BN == 64 && a.tiles_n % 8 == 0 && wbytes >= g_opt.cband_bytes
                 ? a.tiles_n / 8 : 0;
-  a.ngroup = !a.cband && g_ngroup > 0 && a.tiles_n > g_ngroup && a.tiles_n % g_ngroup == 0 && wbytes >= g_cband_bytes
-                 ? (int)g_ngroup : 0;
+  a.ngroup = !a.cband && g_opt.ngroup > 0 && a.tiles_n > g_opt.ngroup && a.tiles_n % g_opt.ngroup == 0 && wbytes >= g_opt.cband_bytes
+                 ? (int)g_opt.ngroup : 0;
   snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_patch<%d, %d, %d, %d, %d, %d, %d, %s, %d, %s, %d, %s%s>",
            BN, WM, WN, S, TH, MINB, UNR, PF ? "true" : "false", ABL, FIRST ? "true" : "false", G,
            UPSKIP ? "true" : "false", f16 ? ", vm::f16_t" : "");
@@ -4860,20 +4851,11 @@ static int launch_patch(ConvArgs& a, hipStream_t st) {
   return check_launch("conv3x3_patch");
 }
 
-static long g_pack_tiled = 1;  // vm_set_option "pack_tiled": 0 = every job on the element-wise pack_weights_batch (A/B)
-static long g_up_skip = 1;  // vm_set_option "up_skip": 0 runs the folded upconvs without the zero-tap skipping (A/B)
-
 // persistent row-slot patch kernel (conv3x3_patch_persist): a resident grid of 8 XCD bands x J walkers, on grids of
-// >= g_persist_rounds full rounds of items (a shorter walk gains no prologue overlap and its last round is ragged);
+// >= g_opt.persist_rounds full rounds of items (a shorter walk gains no prologue overlap and its last round is ragged);
 // the callers check persist_ok, then persist_launch returns 1 when the grid is too small (the caller falls back)
-static long g_patch_persist = 1;
-static long g_persist_rounds = 2;
-static long g_persist_up_rounds = 6;
-static long g_persist_all = 0;  // (A/B) every plain grid of >= persist_rounds rounds
-static long g_persist_rot = 0;  // (A/B) walker rotation: 0 = folded upconvs only, 1 = all, 2 = none
-static long g_persist_half = 1;  // (A/B) halfskip walk for frames whose last tile column is <= 16 px (ConvArgs::halfskip)
 static bool persist_ok(const ConvArgs& a) {
-  return g_patch_persist && g_patch_repi && a.ksplit <= 1 && !a.vstride && a.y_dtype == VM_BF16 &&
+  return g_opt.patch_persist && g_opt.patch_repi && a.ksplit <= 1 && !a.vstride && a.y_dtype == VM_BF16 &&
          (!a.up || a.up_cout % 32 == 0) && (long)a.cout_pad * a.K_pad * 2 < 0x7fff0000L;
 }
 template <int BN, int WM, int WN, int S, int TH, int MINB, bool UPSKIP>
@@ -4898,26 +4880,26 @@ static int launch_patch_persist(ConvArgs& a, hipStream_t st) {
   const long sp = N * ((a.H + C::TH - 1) / C::TH) * ((a.W + C::TW - 1) / C::TW);
   const long resident = (long)per_cu * n_cu;
   // where it pays (same-box A/B per layer of the 1080p forward, 2 blocks per CU = 512 resident): a folded upconv
-  // (phases of 9 / 6 / 6 / 4 taps, rotated over the walkers) needs >= g_persist_up_rounds rounds of items to even
+  // (phases of 9 / 6 / 6 / 4 taps, rotated over the walkers) needs >= g_opt.persist_up_rounds rounds of items to even
   // out (upconv_3 / upconv_4, 8 / 16 rounds: -3 % / -18 %; upconv_2, 4 rounds: +13 %); a plain conv gains on grids of
   // 2..3 rounds (conv4_x, conv5 of 1024 / 512 channels: -2..-3 %) and on the 2-granule K loop (conv2_1: -9 %), and
   // loses a little on 4..8 rounds of 4..8 granules (conv2_2, conv3_2, conv3_3: +2..+3 %)
   const long items = sp * tn;
   bool use;
-  if (a.up) use = items >= g_persist_up_rounds * resident;
-  else use = items >= g_persist_rounds * resident && (items < 3 * resident || a.cin_pad <= 64 || g_persist_rounds == 0 ||
-                                                        g_persist_all);
+  if (a.up) use = items >= g_opt.persist_up_rounds * resident;
+  else use = items >= g_opt.persist_rounds * resident && (items < 3 * resident || a.cin_pad <= 64 || g_opt.persist_rounds == 0 ||
+                                                        g_opt.persist_all);
   if (sp < 8 || resident < 8 || !use || items > 0x7fffffffL) return 1;
   a.tiles_n = tn;
-  a.prot = g_persist_rot == 0 ? (a.up ? 1 : 0) : g_persist_rot == 1 ? 1 : 0;
+  a.prot = g_opt.persist_rot == 0 ? (a.up ? 1 : 0) : g_opt.persist_rot == 1 ? 1 : 0;
   // a last tile column of <= 16 frame columns (135 x 240: 7.5 tiles) costs half a tile: walk those tiles last and
   // serpentine the rounds, so the 2.125 rounds of items of the conv4 level end after ~2.2 tile times instead of 3
   const long J_ = resident / 8;
-  a.halfskip = g_persist_half && C::REMAP && a.W % C::TW != 0 && a.W % C::TW <= 16 && a.W > C::TW;
+  a.halfskip = g_opt.persist_half && C::REMAP && a.W % C::TW != 0 && a.W % C::TW <= 16 && a.W > C::TW;
   if (a.halfskip && !a.prot && J_ % tn == 0) a.prot = 2;
   a.repi = 1;
-  a.prio = (int)g_conv_prio;
-  a.upmask = (int)g_up_skip_mask;
+  a.prio = (int)g_opt.conv_prio;
+  a.upmask = (int)g_opt.up_skip_mask;
   a.tiles_total = (int)(sp * tn);
   const long J = resident / 8;  // walkers per XCD band (every band has >= 2 rounds of items)
   snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_patch_persist<%d, %d, %d, %d, %d, %d, %s>", BN, WM, WN, S,
@@ -4932,18 +4914,17 @@ static int launch_patch_persist(ConvArgs& a, hipStream_t st) {
 template <int BN, int WM, int WN, int S, int TH = 8, int MINB = 1, int UNR = 9, bool PF = false, int ABL = 0,
           bool FIRST = false, int G = 1>
 static int launch_patch_up(ConvArgs& a, hipStream_t st) {
-  if (G > 1 && a.up && g_up_skip) return launch_patch<BN, WM, WN, S, TH, MINB, UNR, PF, ABL, FIRST, G, (G > 1)>(a, st);
+  if (G > 1 && a.up && g_opt.up_skip) return launch_patch<BN, WM, WN, S, TH, MINB, UNR, PF, ABL, FIRST, G, (G > 1)>(a, st);
   return launch_patch<BN, WM, WN, S, TH, MINB, UNR, PF, ABL, FIRST, G, false>(a, st);
 }
 
-// split-K plan of a patch-kernel conv: small grids (under g_splitk_tiles 4 x 32 pixel x 64 channel tiles) with a
+// split-K plan of a patch-kernel conv: small grids (under g_opt.splitk_tiles 4 x 32 pixel x 64 channel tiles) with a
 // long K loop split the channel granules so that ~1024 blocks run; 1 = no split.  Deterministic in the geometry,
 // so vm_conv3x3_workspace_bytes and the launch agree.
-static long g_splitk_tiles = 512;
 static int splitk_plan(long n, int h, int w, int cin_pad, int cout) {
   const long tiles = n * ((h + 3) / 4) * ((w + 31) / 32) * ((cout + 63) / 64);
   const int nch = cin_pad / 32;
-  if (tiles >= g_splitk_tiles || nch < 4 || tiles <= 0) return 1;
+  if (tiles >= g_opt.splitk_tiles || nch < 4 || tiles <= 0) return 1;
   int ks = (int)((1024 + tiles - 1) / tiles);
   if (ks > nch / 2) ks = nch / 2;
   if (ks < 2) return 1;
@@ -4952,16 +4933,14 @@ static int splitk_plan(long n, int h, int w, int cin_pad, int cout) {
 }
 
 // narrow-cout convs (conv3x3_thin): bf16, chunk-major 32-channel granules, 2..16 output channels, no pool / resize
-static long g_thin_kernel = 1;
 static bool thin_ok(int dt, const PackGeom& g, int cout, int x_src_c, int act, const vm_tensor* x) {
-  return g_thin_kernel && dt == VM_BF16 && cout >= 2 && cout <= 16 && g.chunk_major && g.cin_pad % 32 == 0 &&
+  return g_opt.thin_kernel && dt == VM_BF16 && cout >= 2 && cout <= 16 && g.chunk_major && g.cin_pad % 32 == 0 &&
          (x_src_c <= 0 || x_src_c % 32 == 0) && act != VM_ACT_SOFTMAX &&
          (long)x->h * x->w * x->cstride * 2 < 0x7ffffff0L;  // 32-bit byte offsets inside one image
 }
 // narrow-input convs (conv3x3_narrowin): bf16, 8 or 16 tap-major input channels, <= 32 outputs, one source
-static long g_narrowin = 1;
 static bool narrowin_ok(const ConvArgs& a, const PackGeom& g, int cout, int act, const vm_tensor* x, const vm_tensor* y) {
-  return g_narrowin && !g.chunk_major && (g.cin_pad == 8 || g.cin_pad == 16) && cout <= 32 && a.x_src_c <= 0 &&
+  return g_opt.narrowin_kernel && !g.chunk_major && (g.cin_pad == 8 || g.cin_pad == 16) && cout <= 32 && a.x_src_c <= 0 &&
          act != VM_ACT_SOFTMAX && (y->dtype == VM_F32 || y->dtype == VM_BF16) && g.K_pad >= 32 * ((9 * g.cin_pad / 8 + 3) / 4) &&
          (long)x->h * x->w * x->cstride * 2 < 0x7ffffff0L;
 }
@@ -4978,19 +4957,17 @@ static int launch_narrowin(ConvArgs& a, long n, const PackGeom& g, hipStream_t s
   return check_launch("conv3x3_narrowin");
 }
 // split-K plan: below 1024 blocks of 8 x 32 pixels, split the 32-channel chunks over ~thin_blocks (512) blocks
-static long g_thin_th = 8, g_thin_blocks = 512;
 static int thin_splitk_plan(long n, int h, int w, int cin_pad) {
   const long tiles = n * ((h + 7) / 8) * ((w + 31) / 32);  // in 8-row units whatever the tile height
   const int nch = cin_pad / 32;
   if (tiles <= 0 || tiles >= 1024 || nch < 4) return 1;
-  int ks = (int)((g_thin_blocks + tiles - 1) / tiles);
+  int ks = (int)((g_opt.thin_blocks + tiles - 1) / tiles);
   if (ks > nch / 2) ks = nch / 2;
   if (ks < 2) return 1;
   const int per = (nch + ks - 1) / ks;
   return (nch + per - 1) / per;
 }
-// persistent grid: at most g_thin_rounds resident rounds of blocks (0: one block per tile, the r02 launch)
-static long g_thin_rounds = 1;
+// persistent grid: at most g_opt.thin_rounds resident rounds of blocks (0: one block per tile, the r02 launch)
 template <int TH>
 static int thin_resident() {
   static int dev_seen = -1, resident = 0;
@@ -5007,12 +4984,6 @@ static int thin_resident() {
   }
   return resident;
 }
-// the LDS-DMA thin kernel (conv3x3_thin_dma): 0 off; 1 = 8-row tiles, 3-slot ring; 2 = 4-row tiles, 4 slots;
-// 3 = 4-row tiles, 3 slots; 4 = 8-row tiles, 2 slots.  A resident grid of thin_dma_rounds x blocks per CU x CUs
-static long g_thin_dma = 0, g_thin_dma_rounds = 1;
-long g_conv_prio = 0;  // ConvArgs::prio (conv_common.h)
-static long g_thin_rowreuse = 1;  // conv3x3_thin: thin_chunk's row reuse (0: the r03 tap-major loop)
-static long g_thin_twalk = 1;     // conv3x3_thin: XCD-banded tile walk (ConvArgs::twalk; 0: round-robin)
 template <int TH, int S>
 static int launch_thin_dma_cfg(ConvArgs& a, long n, int ks, hipStream_t st) {
   constexpr int lds = thin_dma_lds<TH, S>();
@@ -5032,14 +5003,14 @@ static int launch_thin_dma_cfg(ConvArgs& a, long n, int ks, hipStream_t st) {
   long gx = n * ((a.H + TH - 1) / TH) * (long)((a.W + 31) / 32);
   if (gx > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3_thin_dma: too many tiles");
   a.tiles_total = (int)gx;
-  const long cap = g_thin_dma_rounds * (long)resident / ks;
+  const long cap = g_opt.thin_dma_rounds * (long)resident / ks;
   if (gx > cap) gx = cap < 1 ? 1 : cap;
   snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_thin_dma<%d, %d>", TH, S);
   hipLaunchKernelGGL((conv3x3_thin_dma<TH, S>), dim3((unsigned)gx, ks), dim3(256), lds, st, a);
   return check_launch("conv3x3_thin_dma");
 }
 static int launch_thin_dma(ConvArgs& a, long n, int ks, hipStream_t st) {
-  switch (g_thin_dma) {
+  switch (g_opt.thin_dma) {
     case 2: return launch_thin_dma_cfg<4, 4>(a, n, ks, st);
     case 3: return launch_thin_dma_cfg<4, 3>(a, n, ks, st);
     case 4: return launch_thin_dma_cfg<8, 2>(a, n, ks, st);
@@ -5047,7 +5018,7 @@ static int launch_thin_dma(ConvArgs& a, long n, int ks, hipStream_t st) {
   }
 }
 static int dispatch_thin(ConvArgs& a, long n, hipStream_t st) {
-  const int th = (int)g_thin_th;
+  const int th = (int)g_opt.thin_th;
   const long tiles = n * ((a.H + th - 1) / th) * ((a.W + 31) / 32);
   if (tiles > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3_thin: too many tiles");
   a.tiles_total = (int)tiles;
@@ -5055,11 +5026,11 @@ static int dispatch_thin(ConvArgs& a, long n, hipStream_t st) {
   const int res = th == 16 ? thin_resident<16>() : th == 4 ? thin_resident<4>() : thin_resident<8>();
   if (res < 0) return fail(VM_EHIP, "conv3x3_thin: occupancy query failed");
   long gx = tiles;
-  if (g_thin_rounds > 0 && res > 0) {
-    const long cap = g_thin_rounds * (long)res / ks;
+  if (g_opt.thin_rounds > 0 && res > 0) {
+    const long cap = g_opt.thin_rounds * (long)res / ks;
     if (gx > cap) gx = cap < 1 ? 1 : cap;
   }
-  if (g_thin_dma) {
+  if (g_opt.thin_dma) {
     const int rc = launch_thin_dma(a, n, ks, st);
     if (rc) return rc;
     if (a.ksplit <= 1) return VM_OK;
@@ -5069,8 +5040,8 @@ static int dispatch_thin(ConvArgs& a, long n, hipStream_t st) {
     return check_launch("splitk_reduce");
   }
   const dim3 grid((unsigned)gx, ks);
-  a.twalk = (int)g_thin_twalk;
-  if (!g_thin_rowreuse) {
+  a.twalk = (int)g_opt.thin_twalk;
+  if (!g_opt.thin_rowreuse) {
     snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_thin<%d, false>", th);
     if (th == 16) hipLaunchKernelGGL((conv3x3_thin<16, false>), grid, dim3(256), 0, st, a);
     else if (th == 4) hipLaunchKernelGGL((conv3x3_thin<4, false>), grid, dim3(256), 0, st, a);
@@ -5089,31 +5060,6 @@ static int dispatch_thin(ConvArgs& a, long n, hipStream_t st) {
   return check_launch("splitk_reduce");
 }
 
-// tuning knobs (vm_set_option): conv_kernel 0 = auto, 1 = register-staged only, 2 = LDS-DMA whenever legal;
-// conv_min_tiles = smallest grid (in 256-wide output tiles) for which auto picks the LDS-DMA kernel;
-// glds_rb = K-step bytes of the 256x256 LDS-DMA tile (64: 4-slot ring, 128: 2-slot).
-static long g_conv_kernel = 0;
-static long g_conv_min_tiles = 128;
-static long g_glds_rb = 128;
-static long g_head_kernel = 0;
-static long g_head_th = 16;  // conv3x3_head_mfma tile height for the bf16 128-channel head (8 or 16)
-static long g_patch_cfg = 0;
-#ifdef VM_STUDY
-static long g_softmax_abl = 0;  // conv3x3_first_softmax_f32 timing ablations
-static long g_patch_rowslot = 1;  // 0 = the per-tap-barrier dispatch of r01 (A/B runs)
-static long g_patch_ablate = 0;
-#endif
-static long g_rows_kernel = 1;        // conv_rows.hip: 0 = off, 1 = auto (grid size), 8 / 16 = forced tile height
-static long g_rows_min_blocks = 400;
-static long g_rows_up = 0;            // 1: the folded upconvs too
-static long g_rows_min_cin = 64;       // r04 A/B: conv2_1 (cin 64, 2040 blocks) +0.3 % on rows<16>; below 64 the
-                                       // 2-blocks-per-CU patch kernel hides prologue/epilogue better
-static long g_src_span_limit = 0x7ffffff0L;  // split-source byte span the 32-bit offset kernels take (option
-                                              // "src_span_limit" lowers it for the fallback tests)
-static long g_pair_strip = 1;  // vm_conv3x3_pair_first*: 1 = the strip-walking kernel (conv_pair.hip) where it applies
-static long g_pair_kernel = 0;  // vm_conv3x3_pair_first_nhwc: 0 = persistent weights-resident kernel when cout == 64,
-                                // 1 = streaming patch kernel
-
 static bool patch_ok(const ConvArgs& a, size_t tsize) {
   // bf16 output (16-byte aligned view), or f32 output without the fused pool / folded resize (cout multiple of 4;
   // dword stores when the view is not 16-byte aligned)
@@ -5128,11 +5074,10 @@ static bool patch_ok(const ConvArgs& a, size_t tsize) {
 // the column tiles (8 x 320^2 training crops: the 80 / 40 / 20-wide tower levels, 3 / 2 / 1 tiles per frame -> 2.6
 // / 1.3 / 0.7).  Results are bit-identical (every output keeps its K loop); only which pixels share a block changes.
 // Off for the folded upconvs, odd widths under a fused pool, and where the batch's 32-bit byte offsets would wrap.
-static long g_pack_frames = 1;
 static void plan_packed_frames(ConvArgs& a) {
   a.vstride = a.vW = 0;
   const long N = a.M / ((long)a.H * a.W);
-  if (!g_pack_frames || a.up || N < 2 || (a.py && (a.W & 1))) return;
+  if (!g_opt.pack_frames || a.up || N < 2 || (a.py && (a.W & 1))) return;
   const long plain = N * ((a.W + 31) / 32), packed = (N * (a.W + 2) + 31) / 32;
   if (packed * 10 > plain * 9 || N * (a.W + 2) > 0x7fffffffL) return;
   const long lim = 0x7ffffff0L;
@@ -5156,7 +5101,7 @@ static int dispatch_patch(ConvArgs& a, hipStream_t st) {
     return check_launch("splitk_reduce");
   }
 #ifdef VM_STUDY
-  switch (g_patch_ablate) {  // timing experiments on the default tiling (results are garbage)
+  switch (g_opt.patch_ablate) {  // timing experiments on the default tiling (results are garbage)
     case 1: return launch_patch<64, 8, 1, 6, 8, 1, 9, false, 1>(a, st);
     case 2: return launch_patch<64, 8, 1, 6, 8, 1, 9, false, 2>(a, st);
     case 3: return launch_patch<64, 8, 1, 6, 8, 1, 9, false, 3>(a, st);
@@ -5176,7 +5121,7 @@ static int dispatch_patch(ConvArgs& a, hipStream_t st) {
     default: break;
   }
 #endif
-  switch (g_patch_cfg) {
+  switch (g_opt.patch_cfg) {
     // the tilings the dispatcher below picks (the only ones in the shipped library)
     case 19: return launch_patch_up<64, 8, 1, 3, 8, 1, 9, false, 0, false, 3>(a, st);
     case 22: return launch_patch_up<64, 8, 1, 2, 8, 1, 9, false, 0, false, 3>(a, st);
@@ -5220,12 +5165,12 @@ static int dispatch_patch(ConvArgs& a, hipStream_t st) {
 #endif
     default: break;
   }
-  // row-stationary kernel (conv_rows.hip) on grids of >= g_rows_min_blocks 16 x 32 px x 64 channel blocks (one block
+  // row-stationary kernel (conv_rows.hip) on grids of >= g_opt.rows_min_blocks 16 x 32 px x 64 channel blocks (one block
   // per CU: ~4 full rounds); rows_kernel 8 / 16 forces that tile height wherever it is legal
-  if (g_rows_kernel && rows_ok(a)) {
-    if (g_rows_kernel == 8 || g_rows_kernel == 16) {  // forced: per-frame tiles (the rows kernel does not pack)
+  if (g_opt.rows_kernel && rows_ok(a)) {
+    if (g_opt.rows_kernel == 8 || g_opt.rows_kernel == 16) {  // forced: per-frame tiles (the rows kernel does not pack)
       a.vstride = a.vW = 0;
-      return launch_rows(a, st, (int)g_rows_kernel);
+      return launch_rows(a, st, (int)g_opt.rows_kernel);
     }
     const long N16 = a.M / ((long)a.H * a.W);
     const long blocks16 = N16 * ((a.H + 15) / 16) * ((a.W + 31) / 32) * ((a.cout + 63) / 64);
@@ -5236,8 +5181,8 @@ static int dispatch_patch(ConvArgs& a, hipStream_t st) {
     // ... and only where its 16-row tiles waste no more rows than the patch kernel's 8-row ones (the training
     // towers' 40 x 40 level: 48 of 40 rows vs 40, measured 612 vs ~800 TFLOP/s)
     const bool rows_fit = ((a.H + 15) / 16) * 16 <= ((a.H + 7) / 8) * 8 + a.H / 32;
-    if ((!a.up || g_rows_up) && !a.vstride && rows_fit && blocks16 >= g_rows_min_blocks && a.cin_pad >= g_rows_min_cin &&
-        (a.cin_pad >= 2 * g_rows_min_cin || blocks16 >= 2 * g_rows_min_blocks))
+    if ((!a.up || g_opt.rows_up) && !a.vstride && rows_fit && blocks16 >= g_opt.rows_min_blocks && a.cin_pad >= g_opt.rows_min_cin &&
+        (a.cin_pad >= 2 * g_opt.rows_min_cin || blocks16 >= 2 * g_opt.rows_min_blocks))
       return launch_rows(a, st, 16);
   }
   // measured per layer inside the UNetVideo 1080p forward (scripts/sweep.sh, profiles/r01_patch_cfg_sweep.txt):
@@ -5249,7 +5194,7 @@ static int dispatch_patch(ConvArgs& a, hipStream_t st) {
   const long sp = a.vstride ? ((a.H + 7) / 8) * (long)((a.vW + 31) / 32) : N * ((a.H + 7) / 8) * ((a.W + 31) / 32);
   const long blocks64 = sp * ((a.cout + 63) / 64);
 #ifdef VM_STUDY
-  if (!g_patch_rowslot) {
+  if (!g_opt.patch_rowslot) {
     if (a.cout >= 128 && a.cin_pad >= 256 && sp * ((a.cout + 127) / 128) >= 1000)
       return launch_patch<128, 4, 1, 4, 8, 2>(a, st);
     if (blocks64 < 512) return launch_patch<64, 4, 1, 6, 4>(a, st);
@@ -5257,14 +5202,14 @@ static int dispatch_patch(ConvArgs& a, hipStream_t st) {
   }
 #endif
   // (a folded upconv takes the row-slot configs below, whose instantiation skips its phases' zero taps)
-  if (!(a.up && g_up_skip) && a.cout >= 128 && a.cin_pad >= 512 && sp * ((a.cout + 127) / 128) >= 1000) {
+  if (!(a.up && g_opt.up_skip) && a.cout >= 128 && a.cin_pad >= 512 && sp * ((a.cout + 127) / 128) >= 1000) {
     // fp16 operands (the split x3 forward's upconv_2 / _3, K = 3 x cin): the 3-slot 64-channel ring measured faster
     // (same box, patch_cfg 19 vs auto: 0.759 / 0.803 -> 0.732 / 0.754 ms, profiles/r06k_f16x3_patch_cfg_ab.log)
     if (a.f16) return launch_patch_up<64, 8, 1, 3, 8, 1, 9, false, 0, false, 3>(a, st);
     return launch_patch_up<128, 4, 2, 3, 8, 2>(a, st);  // 64 px x 64 channel waves, 4 per SIMD (r02: -5% vs 4x1)
   }
   if (persist_ok(a)) {  // the same tilings, persistent (2-slot ring: the LDS also holds the block's constants)
-    const bool sk = a.up && g_up_skip;
+    const bool sk = a.up && g_opt.up_skip;
     int rc = 1;
     if (blocks64 >= 512)
       rc = sk ? launch_patch_persist<64, 8, 1, 2, 8, 1, true>(a, st) : launch_patch_persist<64, 8, 1, 2, 8, 1, false>(a, st);
@@ -5274,7 +5219,7 @@ static int dispatch_patch(ConvArgs& a, hipStream_t st) {
   }
   // the 3-slot ring for the largest grids and for the folded upconvs the persistent kernel leaves (upconv_2: its
   // zero-tap phases are latency-bound on the ring, a deeper prefetch measured -2 %)
-  if (blocks64 >= 8000 || (a.up && g_up_skip && blocks64 >= 512))
+  if (blocks64 >= 8000 || (a.up && g_opt.up_skip && blocks64 >= 512))
     return launch_patch_up<64, 8, 1, 3, 8, 1, 9, false, 0, false, 3>(a, st);
   if (blocks64 < 512) return launch_patch_up<64, 4, 1, 2, 4, 2, 9, false, 0, false, 3>(a, st);  // L5: 4 x 32 px tiles
   return launch_patch_up<64, 8, 1, 2, 8, 1, 9, false, 0, false, 3>(a, st);
@@ -5284,7 +5229,7 @@ template <typename T, bool FAST>
 static int dispatch_glds(ConvArgs& a, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
     if (a.cout > 128) {
-      if (g_glds_rb == 64) return launch_glds<T, 64, 256, 256, 2, 4, 4, FAST>(a, st);
+      if (g_opt.glds_rb == 64) return launch_glds<T, 64, 256, 256, 2, 4, 4, FAST>(a, st);
       return launch_glds<T, 128, 256, 256, 2, 4, 2, FAST>(a, st);
     }
   }
@@ -5318,34 +5263,28 @@ static int launch_first(ConvArgs& a, hipStream_t st) {
   return check_launch("conv3x3_first");
 }
 
-static int g_softmax_kernel = 6;  // 0: the generic kernels' softmax epilogue, 1: conv3x3_first_softmax, 2: its NT form,
-                                  // 3 / 4: plain / NT with the per-wave LDS transpose (whole-pixel stores), 5: 4 with
-                                  // LDS weights, 6: wave-private strips (conv3x3_first_softmax_strip, default)
-static long g_softmax_blocks = 2048;  // persistent grid of conv3x3_first_softmax*
-static long g_pair_xin_wide = 1;  // pair kernel, f32 frames with >= 4 channels: two 16-byte loads per pixel (XIN 2)
-
 static int launch_first_softmax(ConvArgs& a, hipStream_t st) {
   const long N = a.M / ((long)a.H * a.W);
   const long sp = N * ((a.H + 7) / 8) * ((a.W + 31) / 32);
   if (sp > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3: too many tiles");
   a.tiles_total = (int)sp;
-  // persistent grid of g_softmax_blocks; tile_of() maps block-order indices in rounds of tiles_n = grid onto
+  // persistent grid of g_opt.softmax_blocks; tile_of() maps block-order indices in rounds of tiles_n = grid onto
   // contiguous per-XCD bands (xcd_tile within a round)
-  const int grid = (int)std::min<long>(sp, g_softmax_blocks);
+  const int grid = (int)std::min<long>(sp, g_opt.softmax_blocks);
   a.tiles_n = grid;
-  if (g_softmax_kernel == 3) {
+  if (g_opt.softmax_kernel == 3) {
     snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax<false, true>");
     hipLaunchKernelGGL((conv3x3_first_softmax<false, true>), dim3(grid), dim3(512), 0, st, a);
-  } else if (g_softmax_kernel == 4) {
+  } else if (g_opt.softmax_kernel == 4) {
     snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax<true, true>");
     hipLaunchKernelGGL((conv3x3_first_softmax<true, true>), dim3(grid), dim3(512), 0, st, a);
-  } else if (g_softmax_kernel == 6) {
+  } else if (g_opt.softmax_kernel == 6) {
     snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax_strip");
     hipLaunchKernelGGL(conv3x3_first_softmax_strip, dim3(grid), dim3(512), 0, st, a);
-  } else if (g_softmax_kernel == 5) {
+  } else if (g_opt.softmax_kernel == 5) {
     snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax<true, true, true>");
     hipLaunchKernelGGL((conv3x3_first_softmax<true, true, true>), dim3(grid), dim3(512), 0, st, a);
-  } else if (g_softmax_kernel == 2) {
+  } else if (g_opt.softmax_kernel == 2) {
     snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax<true>");
     hipLaunchKernelGGL(conv3x3_first_softmax<true>, dim3(grid), dim3(512), 0, st, a);
   } else {
@@ -5355,16 +5294,14 @@ static int launch_first_softmax(ConvArgs& a, hipStream_t st) {
   return check_launch("conv3x3_first_softmax");
 }
 
-static long g_softmax_f32p = 4;  // the pipelined f32 refine kernel's variant (softmax_f32p option); 0: the r03 one
-
 static int launch_first_softmax_f32(ConvArgs& a, int cin, hipStream_t st) {
   const long N = a.M / ((long)a.H * a.W);
   const long sp = N * ((a.H + 7) / 8) * ((a.W + 31) / 32);
   if (sp > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3: too many tiles");
   a.tiles_total = (int)sp;
-  const int grid = (int)std::min<long>(sp, g_softmax_blocks);
+  const int grid = (int)std::min<long>(sp, g_opt.softmax_blocks);
   a.tiles_n = grid;
-  if (g_softmax_f32p && !a.scale && !a.shift) {  // (a scale / shift epilogue: the r03 kernel below)
+  if (g_opt.softmax_f32p && !a.scale && !a.shift) {  // (a scale / shift epilogue: the r03 kernel below)
     // one resident round (2 waves per SIMD: one 512-thread block per CU); softmax_blocks caps it for tests
     static int n_cu = 0;
     if (!n_cu) {
@@ -5373,14 +5310,14 @@ static int launch_first_softmax_f32(ConvArgs& a, int cin, hipStream_t st) {
       if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
         return fail(VM_EHIP, "conv3x3_first_softmax_f32p: CU count query failed");
     }
-    const int gp = (int)std::min<long>(std::min<long>(sp, n_cu), g_softmax_blocks);
+    const int gp = (int)std::min<long>(std::min<long>(sp, n_cu), g_opt.softmax_blocks);
     a.tiles_n = gp;
 #define VM_SMP(C)                                                                             \
   case C:                                                                                    \
     snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax_f32p<%d, 2, false, 0, 18>", C); \
     hipLaunchKernelGGL((conv3x3_first_softmax_f32p<C, 2, false, 0, 18>), dim3(gp), dim3(512), 0, st, a);     \
     break;
-    if (g_softmax_f32p == 6) {  // the row-ring form: segments of a.seg rows x 32-pixel bands, one per wave
+    if (g_opt.softmax_f32p == 6) {  // the row-ring form: segments of a.seg rows x 32-pixel bands, one per wave
       const long nimg = N, bands = (a.W + 31) / 32;
       const long waves = (long)gp * 8;
       long seg = (nimg * bands * a.H + waves - 1) / waves;  // rows per segment for about one item per wave
@@ -5403,9 +5340,9 @@ static int launch_first_softmax_f32(ConvArgs& a, int cin, hipStream_t st) {
       return check_launch("conv3x3_first_softmax_f32r");
     }
 #ifdef VM_STUDY
-    if (cin == 5 && g_softmax_abl) {  // timing ablations (garbage results): 1 no stores, 2 no MFMA, 4 no softmax
-      snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax_f32p<5, 2, false, %ld, 18>", g_softmax_abl);
-      switch (g_softmax_abl) {
+    if (cin == 5 && g_opt.softmax_abl) {  // timing ablations (garbage results): 1 no stores, 2 no MFMA, 4 no softmax
+      snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax_f32p<5, 2, false, %ld, 18>", g_opt.softmax_abl);
+      switch (g_opt.softmax_abl) {
         case 1: hipLaunchKernelGGL((conv3x3_first_softmax_f32p<5, 2, false, 1, 18>), dim3(gp), dim3(512), 0, st, a); break;
         case 2: hipLaunchKernelGGL((conv3x3_first_softmax_f32p<5, 2, false, 2, 18>), dim3(gp), dim3(512), 0, st, a); break;
         case 3: hipLaunchKernelGGL((conv3x3_first_softmax_f32p<5, 2, false, 3, 18>), dim3(gp), dim3(512), 0, st, a); break;
@@ -5417,7 +5354,7 @@ static int launch_first_softmax_f32(ConvArgs& a, int cin, hipStream_t st) {
       return check_launch("conv3x3_first_softmax_f32p");
     }
 #endif
-    if (cin <= 5 && g_softmax_f32p == 7) {  // split-bf16 x6 on the bf16 MFMA (f32 accuracy; X6 above)
+    if (cin <= 5 && g_opt.softmax_f32p == 7) {  // split-bf16 x6 on the bf16 MFMA (f32 accuracy; X6 above)
       switch (cin) {
 #define VM_SMX(C)                                                                                        \
   case C:                                                                                                \
@@ -5430,13 +5367,13 @@ static int launch_first_softmax_f32(ConvArgs& a, int cin, hipStream_t st) {
       }
       return check_launch("conv3x3_first_softmax_f32p");
     }
-    if (cin == 5 && g_softmax_f32p == 2) {
+    if (cin == 5 && g_opt.softmax_f32p == 2) {
       snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax_f32p<5, 4>");
       hipLaunchKernelGGL((conv3x3_first_softmax_f32p<5, 4>), dim3(gp), dim3(512), 0, st, a);
       return check_launch("conv3x3_first_softmax_f32p");
     }
-    if (cin == 5 && g_softmax_f32p >= 4) {  // LDS-transposed whole-pixel stores: 4 non-temporal, 5 through L2
-      if (g_softmax_f32p == 4) {
+    if (cin == 5 && g_opt.softmax_f32p >= 4) {  // LDS-transposed whole-pixel stores: 4 non-temporal, 5 through L2
+      if (g_opt.softmax_f32p == 4) {
         snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax_f32p<5, 2, false, 0, 18>");
         hipLaunchKernelGGL((conv3x3_first_softmax_f32p<5, 2, false, 0, 18>), dim3(gp), dim3(512), 0, st, a);
       } else {
@@ -5445,12 +5382,12 @@ static int launch_first_softmax_f32(ConvArgs& a, int cin, hipStream_t st) {
       }
       return check_launch("conv3x3_first_softmax_f32p");
     }
-    if (cin == 5 && g_softmax_f32p == 1) {  // stores straight from the accumulator lanes through L2 (A/B)
+    if (cin == 5 && g_opt.softmax_f32p == 1) {  // stores straight from the accumulator lanes through L2 (A/B)
       snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax_f32p<5>");
       hipLaunchKernelGGL((conv3x3_first_softmax_f32p<5>), dim3(gp), dim3(512), 0, st, a);
       return check_launch("conv3x3_first_softmax_f32p");
     }
-    if (cin == 5 && g_softmax_f32p == 3) {  // non-temporal stores (A/B)
+    if (cin == 5 && g_opt.softmax_f32p == 3) {  // non-temporal stores (A/B)
       snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax_f32p<5, 2, false, 0, 2>");
       hipLaunchKernelGGL((conv3x3_first_softmax_f32p<5, 2, false, 0, 2>), dim3(gp), dim3(512), 0, st, a);
       return check_launch("conv3x3_first_softmax_f32p");
@@ -5468,10 +5405,10 @@ static int launch_first_softmax_f32(ConvArgs& a, int cin, hipStream_t st) {
     hipLaunchKernelGGL(conv3x3_first_softmax_f32<C>, dim3(grid), dim3(512), 0, st, a);      \
     break;
 #ifdef VM_STUDY
-  if (cin == 5 && g_softmax_abl) {  // timing ablations of the f32 refine kernel (results are garbage)
-    snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax_f32<5, %ld>", g_softmax_abl);
-    if (g_softmax_abl == 1) hipLaunchKernelGGL((conv3x3_first_softmax_f32<5, 1>), dim3(grid), dim3(512), 0, st, a);
-    else if (g_softmax_abl == 2) hipLaunchKernelGGL((conv3x3_first_softmax_f32<5, 2>), dim3(grid), dim3(512), 0, st, a);
+  if (cin == 5 && g_opt.softmax_abl) {  // timing ablations of the f32 refine kernel (results are garbage)
+    snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_first_softmax_f32<5, %ld>", g_opt.softmax_abl);
+    if (g_opt.softmax_abl == 1) hipLaunchKernelGGL((conv3x3_first_softmax_f32<5, 1>), dim3(grid), dim3(512), 0, st, a);
+    else if (g_opt.softmax_abl == 2) hipLaunchKernelGGL((conv3x3_first_softmax_f32<5, 2>), dim3(grid), dim3(512), 0, st, a);
     else hipLaunchKernelGGL((conv3x3_first_softmax_f32<5, 3>), dim3(grid), dim3(512), 0, st, a);
     return check_launch("conv3x3_first_softmax_f32");
   }
@@ -5487,281 +5424,124 @@ static int launch_first_softmax_f32(ConvArgs& a, int cin, hipStream_t st) {
 template <typename T>
 static int dispatch_mfma(ConvArgs& a, hipStream_t st, int cin = 0) {
   // f32 refine conv + softmax (cin <= 8 of a 16-byte-aligned 8-float pixel, 64 outputs, f32 out)
-  if (sizeof(T) == 4 && g_softmax_kernel != 0 && g_conv_kernel != 1 && g_conv_kernel != 2 && cin > 0 && cin <= 8 &&
+  if (sizeof(T) == 4 && g_opt.softmax_kernel != 0 && g_opt.conv_kernel != 1 && g_opt.conv_kernel != 2 && cin > 0 && cin <= 8 &&
       a.cin_pad == 8 && !a.chunk_major && a.x_src_c <= 0 && a.y_dtype == VM_F32 && a.y_vec && a.act == VM_ACT_SOFTMAX &&
       a.cout == 64 && a.K_pad == 96 && a.x_cstride % 4 == 0 && a.x_coff % 4 == 0 &&
       reinterpret_cast<uintptr_t>(a.x) % 16 == 0)
     return launch_first_softmax_f32(a, cin, st);
-  if (sizeof(T) == 2 && g_softmax_kernel != 0 && g_conv_kernel != 1 && g_conv_kernel != 2 && a.cin_pad == 8 &&
+  if (sizeof(T) == 2 && g_opt.softmax_kernel != 0 && g_opt.conv_kernel != 1 && g_opt.conv_kernel != 2 && a.cin_pad == 8 &&
       !a.chunk_major && a.x_src_c <= 0 && a.y_dtype == VM_F32 && a.y_vec && a.act == VM_ACT_SOFTMAX && a.cout == 64 &&
       a.K_pad == 128)
     return launch_first_softmax(a, st);
-  if (sizeof(T) == 2 && g_conv_kernel != 1 && g_conv_kernel != 2 && a.cin_pad == 8 && !a.chunk_major && a.x_src_c <= 0 &&
+  if (sizeof(T) == 2 && g_opt.conv_kernel != 1 && g_opt.conv_kernel != 2 && a.cin_pad == 8 && !a.chunk_major && a.x_src_c <= 0 &&
       a.y_dtype == VM_BF16 && a.y_vec && a.act != VM_ACT_SOFTMAX && (a.cout & 7) == 0 && a.K_pad == 128)
     return launch_first(a, st);
-  if ((g_conv_kernel == 0 || g_conv_kernel == 3) && patch_ok(a, sizeof(T))) return dispatch_patch(a, st);
-  if (g_conv_kernel != 1 && a.act != VM_ACT_SOFTMAX && a.x_src_c <= 0) {
+  if ((g_opt.conv_kernel == 0 || g_opt.conv_kernel == 3) && patch_ok(a, sizeof(T))) return dispatch_patch(a, st);
+  if (g_opt.conv_kernel != 1 && a.act != VM_ACT_SOFTMAX && a.x_src_c <= 0) {
     // measured (tools/convbench.py): the LDS-DMA kernel wins for cout >= 256 (256x256 tiles); for
     // cout <= 128 its 64-channel-wide waves are DMA-issue-bound and the register-staged kernel is faster
     const int bm = a.cout > 64 ? 256 : 512;
     const long tiles = ((a.M + bm - 1) / bm) * ((a.cout + 255) / 256);
     const bool wide = sizeof(T) == 2 && a.cout > 128;
-    if (g_conv_kernel == 2 || (wide && tiles >= g_conv_min_tiles))
+    if (g_opt.conv_kernel == 2 || (wide && tiles >= g_opt.conv_min_tiles))
       return a.chunk_major ? dispatch_glds<T, true>(a, st) : dispatch_glds<T, false>(a, st);
   }
   if (a.cout <= 64) return launch_mfma<T, 256, 64>(a, st);
   return launch_mfma<T, 128, 128>(a, st);
 }
 
+
+// every key of g_opt; the shipped library has neither the study-only keys nor the study tilings' values.  A value is
+// accepted if any entry of its key accepts it.
+static const OptDef conv_options[] = {
+    {"conv_kernel", &g_opt.conv_kernel, OPT_RANGE, 2, {0, 3}},
+    {"softmax_kernel", &g_opt.softmax_kernel, OPT_RANGE, 2, {0, 6}},
+    {"softmax_blocks", &g_opt.softmax_blocks, OPT_RANGE, 2, {1, 1 << 20}},
+    {"head_th", &g_opt.head_th, OPT_SET, 2, {8, 16}},
+    {"softmax_f32p", &g_opt.softmax_f32p, OPT_RANGE, 2, {0, 7}},
+    {"cband", &g_opt.cband, OPT_RANGE, 2, {0, 2}},
+    {"ngroup", &g_opt.ngroup, OPT_RANGE, 2, {0, 64}},
+    {"cband_bytes", &g_opt.cband_bytes, OPT_ANY},
+    {"rows_kernel", &g_opt.rows_kernel, OPT_SET, 4, {0, 1, 8, 16}},
+    {"pack_tiled", &g_opt.pack_tiled, OPT_ANY},
+    {"persist_half", &g_opt.persist_half, OPT_ANY},
+    {"rows_up", &g_opt.rows_up, OPT_ANY},
+    {"rows_min_cin", &g_opt.rows_min_cin, OPT_ANY},
+    {"rows_min_blocks", &g_opt.rows_min_blocks, OPT_ANY},
+    {"thin_rounds", &g_opt.thin_rounds, OPT_RANGE, 2, {0, 64}},
+    {"pack_frames", &g_opt.pack_frames, OPT_RANGE, 2, {0, 1}},
+    {"up_skip", &g_opt.up_skip, OPT_RANGE, 2, {0, 1}},
+    {"src_span_limit", &g_opt.src_span_limit, OPT_RANGE, 2, {1, 0x7ffffff0L}},
+    {"thin_blocks", &g_opt.thin_blocks, OPT_ANY},
+    {"thin_th", &g_opt.thin_th, OPT_SET, 3, {4, 8, 16}},
+    {"conv_prio", &g_opt.conv_prio, OPT_RANGE, 2, {0, 1}},
+    {"thin_twalk", &g_opt.thin_twalk, OPT_RANGE, 2, {0, 1}},
+    {"thin_rowreuse", &g_opt.thin_rowreuse, OPT_RANGE, 2, {0, 1}},
+    {"thin_dma", &g_opt.thin_dma, OPT_RANGE, 2, {0, 4}},  // 0: conv3x3_thin; 1..4: conv3x3_thin_dma configs
+    {"thin_dma_rounds", &g_opt.thin_dma_rounds, OPT_RANGE, 2, {1, 64}},
+    {"narrowin_kernel", &g_opt.narrowin_kernel, OPT_RANGE, 2, {0, 1}},
+    {"thin_kernel", &g_opt.thin_kernel, OPT_RANGE, 2, {0, 1}},
+    {"conv_min_tiles", &g_opt.conv_min_tiles, OPT_ANY},
+#ifdef VM_STUDY
+    {"patch_cfg", &g_opt.patch_cfg, OPT_RANGE, 2, {0, 31}},
+    {"patch_ablate", &g_opt.patch_ablate, OPT_ANY},  // timing-only ablations: garbage results
+    {"softmax_abl", &g_opt.softmax_abl, OPT_ANY},    // timing-only ablations of the f32 refine kernel
+    {"patch_rowslot", &g_opt.patch_rowslot, OPT_RANGE, 2, {0, 1}},
+    {"pair_strip_abl", &g_opt.pair_strip_abl, OPT_ANY},  // timing-only ablations of the strip pair kernel
+    {"pair_kernel", &g_opt.pair_kernel, OPT_RANGE, 2, {0, 1}},
+    {"pair_kernel", &g_opt.pair_kernel, OPT_RANGE, 2, {10, 18}},  // conv3x3_pair_persist's timing ablations
+#else
+    {"patch_cfg", &g_opt.patch_cfg, OPT_SET, 5, {0, 19, 22, 25, 30}, " (other tilings: the study build)"},
+    {"pair_kernel", &g_opt.pair_kernel, OPT_RANGE, 2, {0, 1}, " (ablations: the study build)"},
+#endif
+    {"pair_xin_wide", &g_opt.pair_xin_wide, OPT_RANGE, 2, {0, 1}},
+    {"border_ks", &g_opt.border_ks, OPT_SET, 3, {1, 2, 4}},
+    {"patch_repi", &g_opt.patch_repi, OPT_RANGE, 2, {0, 1}},
+    {"persist_rounds", &g_opt.persist_rounds, OPT_RANGE, 2, {0, 64}, " (0: any grid)"},
+    {"persist_up_rounds", &g_opt.persist_up_rounds, OPT_RANGE, 2, {0, 64}, " (0: any grid)"},
+    {"persist_all", &g_opt.persist_all, OPT_RANGE, 2, {0, 2}},
+    {"persist_rot", &g_opt.persist_rot, OPT_RANGE, 2, {0, 2}},
+    {"up_skip_mask", &g_opt.up_skip_mask, OPT_RANGE, 2, {0, 3}},
+    {"patch_persist", &g_opt.patch_persist, OPT_RANGE, 2, {0, 1}},
+    {"pair_strip_pin", &g_opt.pair_strip_pin, OPT_RANGE, 2, {0, 1}},
+    {"pair_strip", &g_opt.pair_strip, OPT_RANGE, 2, {0, 1}},
+    {"head_kernel", &g_opt.head_kernel, OPT_RANGE, 2, {0, 2}},
+    {"splitk_tiles", &g_opt.splitk_tiles, OPT_ANY},
+    {"glds_rb", &g_opt.glds_rb, OPT_SET, 2, {64, 128}},
+    {nullptr},
+};
 }  // namespace vm
 
 using namespace vm;
 
+// VM_OK / VM_EINVAL, or 1 when the table has no entry for the key
+static int set_from(const OptDef* t, const char* key, long value) {
+  char want[160] = "";
+  const char* note = "";
+  for (; t->key; ++t) {
+    if (strcmp(key, t->key)) continue;
+    bool ok = t->kind == OPT_ANY || (t->kind == OPT_RANGE && value >= t->v[0] && value <= t->v[1]);
+    for (int i = 0; t->kind == OPT_SET && i < t->n; ++i) ok = ok || value == t->v[i];
+    if (ok) {
+      *t->value = value;
+      return VM_OK;
+    }
+    size_t len = strlen(want);
+    if (len) len += snprintf(want + len, sizeof want - len, " or ");
+    if (t->kind == OPT_RANGE) snprintf(want + len, sizeof want - len, "%ld..%ld", t->v[0], t->v[1]);
+    for (int i = 0; t->kind == OPT_SET && i < t->n && len < sizeof want; ++i)
+      len += snprintf(want + len, sizeof want - len, i == 0 ? "%ld" : i + 1 < t->n ? ", %ld" : " or %ld", t->v[i]);
+    if (t->note) note = t->note;
+  }
+  return want[0] ? fail(VM_EINVAL, "set_option: %s must be %s%s", key, want, note) : 1;
+}
+
 extern "C" int vm_set_option(const char* key, long value) {
   if (!key) return fail(VM_EINVAL, "set_option: NULL key");
-  if (!strcmp(key, "conv_kernel")) {
-    if (value < 0 || value > 3) return fail(VM_EINVAL, "conv_kernel must be 0..3");
-    g_conv_kernel = value;
-    return VM_OK;
+  for (const OptDef* t : {conv_options, bn_options, train_options}) {
+    const int rc = set_from(t, key, value);
+    if (rc != 1) return rc;
   }
-  if (!strcmp(key, "softmax_kernel")) {
-    if (value < 0 || value > 6) return fail(VM_EINVAL, "softmax_kernel must be 0..6");
-    g_softmax_kernel = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "softmax_blocks")) {
-    if (value < 1 || value > (1 << 20)) return fail(VM_EINVAL, "softmax_blocks must be 1..2^20");
-    g_softmax_blocks = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "head_th")) {
-    if (value != 8 && value != 16) return fail(VM_EINVAL, "head_th must be 8 or 16");
-    g_head_th = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "softmax_f32p")) {  // 0 the r03 kernel; 1 pipelined; 2 its 4-waves-per-SIMD build; 3 NT stores;
-                                       // 4 / 5 LDS-transposed whole-pixel stores, NT / through L2;
-                                       // 6 the row-ring form (conv3x3_first_softmax_f32r); 7 split-bf16 x6
-    if (value < 0 || value > 7) return fail(VM_EINVAL, "softmax_f32p must be 0..7");
-    g_softmax_f32p = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "cband")) {
-    if (value < 0 || value > 2) return fail(VM_EINVAL, "cband must be 0, 1 or 2");
-    g_cband = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "ngroup")) {
-    if (value < 0 || value > 64) return fail(VM_EINVAL, "ngroup must be 0..64");
-    g_ngroup = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "cband_bytes")) {
-    g_cband_bytes = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "rows_kernel")) {
-    if (value != 0 && value != 1 && value != 8 && value != 16) return fail(VM_EINVAL, "rows_kernel must be 0, 1, 8 or 16");
-    g_rows_kernel = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "pack_tiled")) {
-    g_pack_tiled = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "persist_half")) {
-    g_persist_half = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "rows_up")) {
-    g_rows_up = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "rows_min_cin")) {
-    g_rows_min_cin = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "rows_min_blocks")) {
-    g_rows_min_blocks = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "thin_rounds")) {
-    if (value < 0 || value > 64) return fail(VM_EINVAL, "thin_rounds must be 0..64");
-    g_thin_rounds = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "pack_frames")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "pack_frames must be 0 or 1");
-    g_pack_frames = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "up_skip")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "up_skip must be 0 or 1");
-    g_up_skip = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "src_span_limit")) {
-    if (value < 1 || value > 0x7ffffff0L) return fail(VM_EINVAL, "src_span_limit must be 1..0x7ffffff0");
-    g_src_span_limit = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "thin_blocks")) {
-    g_thin_blocks = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "thin_th")) {
-    if (value != 4 && value != 8 && value != 16) return fail(VM_EINVAL, "thin_th must be 4, 8 or 16");
-    g_thin_th = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "conv_prio")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "conv_prio must be 0 or 1");
-    g_conv_prio = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "thin_twalk")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "thin_twalk must be 0 or 1");
-    g_thin_twalk = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "thin_rowreuse")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "thin_rowreuse must be 0 or 1");
-    g_thin_rowreuse = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "thin_dma")) {  // 0: conv3x3_thin; 1..4: conv3x3_thin_dma configs (launch_thin_dma)
-    if (value < 0 || value > 4) return fail(VM_EINVAL, "thin_dma must be 0..4");
-    g_thin_dma = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "thin_dma_rounds")) {
-    if (value < 1 || value > 64) return fail(VM_EINVAL, "thin_dma_rounds must be 1..64");
-    g_thin_dma_rounds = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "narrowin_kernel")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "narrowin_kernel must be 0 or 1");
-    g_narrowin = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "thin_kernel")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "thin_kernel must be 0 or 1");
-    g_thin_kernel = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "conv_min_tiles")) {
-    g_conv_min_tiles = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "patch_cfg")) {
-#ifdef VM_STUDY
-    if (value < 0 || value > 31) return fail(VM_EINVAL, "patch_cfg must be 0..31");
-#else
-    if (value != 0 && value != 19 && value != 22 && value != 25 && value != 30)
-      return fail(VM_EINVAL, "patch_cfg must be 0, 19, 22, 25 or 30 (other tilings: the study build, make study)");
-#endif
-    g_patch_cfg = value;
-    return VM_OK;
-  }
-#ifdef VM_STUDY
-  if (!strcmp(key, "patch_ablate")) {  // timing-only ablations: garbage results
-    g_patch_ablate = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "softmax_abl")) {  // timing-only ablations of the f32 refine kernel: garbage results
-    g_softmax_abl = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "patch_rowslot")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "patch_rowslot must be 0 or 1");
-    g_patch_rowslot = value;
-    return VM_OK;
-  }
-#endif
-  if (!strcmp(key, "pair_xin_wide")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "pair_xin_wide must be 0 or 1");
-    g_pair_xin_wide = value;
-    return VM_OK;
-  }
-#ifdef VM_STUDY
-  if (!strcmp(key, "pair_strip_abl")) {  // timing-only ablations of the strip pair kernel (garbage results)
-    vm::g_pair_strip_abl = value;
-    return VM_OK;
-  }
-#endif
-  if (!strcmp(key, "border_ks")) {
-    if (value != 1 && value != 2 && value != 4) return fail(VM_EINVAL, "border_ks must be 1, 2 or 4");
-    g_border_ks = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "patch_repi")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "patch_repi must be 0 or 1");
-    g_patch_repi = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "persist_rounds") || !strcmp(key, "persist_up_rounds")) {
-    if (value < 0 || value > 64) return fail(VM_EINVAL, "%s must be in 0..64 (0: any grid)", key);
-    (key[8] == 'u' ? g_persist_up_rounds : g_persist_rounds) = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "persist_all") || !strcmp(key, "persist_rot")) {
-    if (value < 0 || value > 2) return fail(VM_EINVAL, "%s must be 0, 1 or 2", key);
-    (key[8] == 'a' ? g_persist_all : g_persist_rot) = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "up_skip_mask")) {
-    if (value < 0 || value > 3) return fail(VM_EINVAL, "up_skip_mask must be 0..3");
-    g_up_skip_mask = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "patch_persist")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "patch_persist must be 0 or 1");
-    g_patch_persist = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "pair_strip_pin")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "pair_strip_pin must be 0 or 1");
-    vm::g_pair_strip_pin = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "pair_strip")) {
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "pair_strip must be 0 or 1");
-    g_pair_strip = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "pair_kernel")) {
-#ifdef VM_STUDY
-    if (value < 0 || (value > 1 && value < 10) || value > 18) return fail(VM_EINVAL, "pair_kernel must be 0, 1 or 10..18");
-#else
-    if (value < 0 || value > 1) return fail(VM_EINVAL, "pair_kernel must be 0 or 1 (ablations: the study build)");
-#endif
-    g_pair_kernel = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "head_kernel")) {
-    if (value < 0 || value > 2) return fail(VM_EINVAL, "head_kernel must be 0, 1 or 2");
-    g_head_kernel = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "splitk_tiles")) {
-    g_splitk_tiles = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "glds_rb")) {
-    if (value != 64 && value != 128) return fail(VM_EINVAL, "glds_rb must be 64 or 128");
-    g_glds_rb = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "bn_vec_fwd")) {
-    g_bn_vec_fwd = value;
-    return VM_OK;
-  }
-  if (!strcmp(key, "bn_blocks")) {
-    if (value < 1 || value > BN_TARGET_MAX) return fail(VM_EINVAL, "set_option: bn_blocks must be 1..%d", BN_TARGET_MAX);
-    g_bn_target = value;
-    return VM_OK;
-  }
-  if (train_set_option(key, value)) return VM_OK;
   return fail(VM_EINVAL, "set_option: unknown key '%s'", key);
 }
 
@@ -5818,7 +5598,7 @@ extern "C" int vm_conv3x3_pack_weights_batch(int njobs, const vm_pack_job* jobs,
     for (int i = 0; i < njobs; ++i) {
       const vm_pack_job& j = jobs[i];
       const PackGeom g = geom(j.cin, j.cout, j.dtype);
-      const bool vec = g_pack_tiled && j.dtype == VM_BF16 && g.chunk_major &&
+      const bool vec = g_opt.pack_tiled && j.dtype == VM_BF16 && g.chunk_major &&
                        reinterpret_cast<uintptr_t>(j.packed) % 16 == 0;
       const int kind = !vec ? 0 : j.flip ? 2 : 1;
       if (kind != tiled) continue;
@@ -5846,15 +5626,33 @@ struct SplitOut {
   int* ovf;
 };
 
-static int conv_impl(const vm_tensor* x, const void* packed, int cin, int cout, const float* bias, const float* scale,
-                     const float* shift, int act, vm_tensor* y, const vm_tensor* yp, void* stream,
-                     float* y2 = nullptr, int nsrc = 0, long src_stride = 0, void* work = nullptr,
-                     size_t work_bytes = 0, const float* head_part = nullptr, const float* y_acc = nullptr,
-                     const SplitOut* so = nullptr);
+// One conv call as the C entry points hand it to conv_impl: the arguments every entry point has, then the optional ones
+struct ConvCall {
+  const vm_tensor* x;
+  const void* packed;
+  int cin, cout;
+  const float* bias;
+  const float* scale;
+  const float* shift;
+  int act;
+  vm_tensor* y;
+  void* stream;
+  const vm_tensor* yp = nullptr;  // fused 2x2/2 SAME max-pool output
+  float* y2 = nullptr;            // cout == 1: sigmoid of the pre-activation value (HeadArgs::y2)
+  int nsrc = 0;                   // > 1: split sources, x the view of source 0, source s at s * src_stride elements
+  long src_stride = 0;
+  void* work = nullptr;           // split-K workspace (vm_conv3x3_workspace_bytes)
+  size_t work_bytes = 0;
+  const float* head_part = nullptr;  // cout == 1: HeadArgs::part
+  const float* y_acc = nullptr;      // cout == 1: HeadArgs::yacc
+  const SplitOut* so = nullptr;      // split-fp16 x3 output
+};
+
+static int conv_impl(const ConvCall& c);
 
 extern "C" int vm_conv3x3_nhwc(const vm_tensor* x, const void* packed, int cin, int cout, const float* bias,
                                const float* scale, const float* shift, int act, vm_tensor* y, void* stream) {
-  return conv_impl(x, packed, cin, cout, bias, scale, shift, act, y, nullptr, stream);
+  return conv_impl({x, packed, cin, cout, bias, scale, shift, act, y, stream});
 }
 
 extern "C" int vm_conv3x3_sources_nhwc(const vm_tensor* x, int nsrc, long src_stride, const void* packed, int cin,
@@ -5862,7 +5660,10 @@ extern "C" int vm_conv3x3_sources_nhwc(const vm_tensor* x, int nsrc, long src_st
                                        vm_tensor* y, void* stream) {
   if (nsrc < 1 || (nsrc > 1 && src_stride <= 0)) return fail(VM_EINVAL, "conv3x3_sources: nsrc %d stride %ld", nsrc,
                                                             src_stride);
-  return conv_impl(x, packed, cin, cout, bias, scale, shift, act, y, nullptr, stream, nullptr, nsrc, src_stride);
+  ConvCall c{x, packed, cin, cout, bias, scale, shift, act, y, stream};
+  c.nsrc = nsrc;
+  c.src_stride = src_stride;
+  return conv_impl(c);
 }
 
 extern "C" int vm_conv3x3_pool_nhwc(const vm_tensor* x, const void* packed, int cin, int cout, const float* bias,
@@ -5872,7 +5673,9 @@ extern "C" int vm_conv3x3_pool_nhwc(const vm_tensor* x, const void* packed, int 
   if (ypool->n != y->n || ypool->h != (y->h + 1) / 2 || ypool->w != (y->w + 1) / 2 || ypool->c != cout ||
       ypool->dtype != y->dtype)
     return fail(VM_EINVAL, "conv3x3_pool: pool output must be [n, ceil(h/2), ceil(w/2), cout] in the output dtype");
-  return conv_impl(x, packed, cin, cout, bias, scale, shift, act, y, ypool, stream);
+  ConvCall c{x, packed, cin, cout, bias, scale, shift, act, y, stream};
+  c.yp = ypool;
+  return conv_impl(c);
 }
 
 extern "C" int vm_conv3x3_fold_up2x_weights(const float* w_hwio, int cin, int cout, float* w_up_hwio, void* stream) {
@@ -5907,7 +5710,7 @@ extern "C" int vm_conv3x3_up2x_nhwc(const vm_tensor* x, const void* packed_up, c
                     x->coff + g.cin_pad <= x->cstride;
   const bool yvec = reinterpret_cast<uintptr_t>(y->ptr) % 16 == 0 && y->cstride % 8 == 0 && y->coff % 8 == 0;
   if (x->dtype != VM_BF16 || y->dtype != VM_BF16 || cout % 64 || !xvec || !yvec || act == VM_ACT_SOFTMAX ||
-      g_conv_kernel == 1 || g_conv_kernel == 2)
+      g_opt.conv_kernel == 1 || g_opt.conv_kernel == 2)
     return fail(VM_EUNSUPPORTED, "conv3x3_up2x: folded resize needs the bf16 patch kernel (cout %% 64 == 0, "
                                  "16-byte channel views)");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -5935,9 +5738,9 @@ extern "C" int vm_conv3x3_up2x_nhwc(const vm_tensor* x, const void* packed_up, c
   b.nb = 2 * OW + 2 * (OH - 2);
   const long nblk = ((long)x->n * b.nb + 15) / 16;
   if (nblk > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3_up2x: too many border pixels");
-  if (g_border_ks == 4)
+  if (g_opt.border_ks == 4)
     hipLaunchKernelGGL(conv3x3_up2x_border<4>, dim3((unsigned)nblk, cout / 64), dim3(1024), 0, st, b);
-  else if (g_border_ks == 2)
+  else if (g_opt.border_ks == 2)
     hipLaunchKernelGGL(conv3x3_up2x_border<2>, dim3((unsigned)nblk, cout / 64), dim3(512), 0, st, b);
   else
     hipLaunchKernelGGL(conv3x3_up2x_border<1>, dim3((unsigned)nblk, cout / 64), dim3(256), 0, st, b);
@@ -5965,7 +5768,7 @@ extern "C" int vm_conv3x3_up2x_split3_nhwc(const vm_tensor* x, const void* packe
   const PackGeom g = geom(cin, 4 * cout, VM_F16), g1 = geom(cin, cout, VM_F16);
   const bool xvec = reinterpret_cast<uintptr_t>(x->ptr) % 16 == 0 && x->cstride % 8 == 0 && x->coff % 8 == 0 &&
                     x->coff + x->c <= x->cstride;
-  if (cout % 64 || !xvec || !split3_view_ok(y, ys, cout) || !g_up_skip || g_conv_kernel == 1 || g_conv_kernel == 2)
+  if (cout % 64 || !xvec || !split3_view_ok(y, ys, cout) || !g_opt.up_skip || g_opt.conv_kernel == 1 || g_opt.conv_kernel == 2)
     return fail(VM_EUNSUPPORTED, "conv3x3_up2x_split3: cout %% 64 == 0, 16-byte channel views, the split layout");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   ConvArgs a{};
@@ -6008,7 +5811,7 @@ extern "C" int vm_conv3x3_up2x_head_nhwc(const vm_tensor* x, const void* packed_
     return fail(VM_EINVAL, "conv3x3_up2x_head: head filter [3,3,%d,1] with the conv's %d channels at %d", head_cin, cout,
                 head_coff);
   // the partials come from the patch kernel's register epilogue (64-channel row-slot tilings)
-  if (!g_patch_repi || g_patch_cfg || g_rows_up || !g_up_skip)
+  if (!g_opt.patch_repi || g_opt.patch_cfg || g_opt.rows_up || !g_opt.up_skip)
     return fail(VM_EUNSUPPORTED, "conv3x3_up2x_head: needs the patch kernel's register epilogue");
   g_up_head = {head_w, head_cin, head_coff, partial, store_y ? 0 : 1};
   const int rc = vm_conv3x3_up2x_nhwc(x, packed_up, packed, cin, cout, bias, scale, shift, act, y, stream);
@@ -6036,7 +5839,7 @@ template <int PABL, int XIN = 2>
 static int launch_pair_persist(ConvArgs& a, long sp, hipStream_t st) {
   if constexpr (XIN == 2) {
     if (!a.x_f32) return launch_pair_persist<PABL, 0>(a, sp, st);
-    if (a.x_c < 4 || !g_pair_xin_wide) return launch_pair_persist<PABL, 1>(a, sp, st);
+    if (a.x_c < 4 || !g_opt.pair_xin_wide) return launch_pair_persist<PABL, 1>(a, sp, st);
   }
   static int attr_dev = -1, n_cu = 0;
   int dev = 0;
@@ -6054,10 +5857,29 @@ static int launch_pair_persist(ConvArgs& a, long sp, hipStream_t st) {
   return check_launch("conv3x3_pair_persist");
 }
 
-static int pair_first_impl(const vm_tensor* x, const void* packed1, int cin1, const float* bias1, const void* packed2,
-                           int cout2, const float* bias2, const float* scale2, const float* shift2, int act2,
-                           vm_tensor* y, vm_tensor* ypool, const float* head_w, int head_cin, int head_coff,
-                           float* partial, int store_y, void* stream, vm_tensor* mid = nullptr);
+// One call of the conv1_1 -> conv1_2 pair (vm_conv3x3_pair_first*)
+struct PairCall {
+  const vm_tensor* x;
+  const void* packed1;
+  int cin1;
+  const float* bias1;
+  const void* packed2;
+  int cout2;
+  const float* bias2;
+  const float* scale2;
+  const float* shift2;
+  int act2;
+  vm_tensor* y;
+  vm_tensor* ypool;
+  void* stream;
+  const float* head_w = nullptr;  // head split: conv1_5's HWIO f32 filter, head_cin input channels, ours at head_coff
+  int head_cin = 0, head_coff = 0;
+  float* partial = nullptr;       // ... its per-tap partials [pixel][12]; store_y = 0 leaves y unwritten
+  int store_y = 1;
+  vm_tensor* mid = nullptr;       // conv1_1's output too (the strip kernel only)
+};
+
+static int pair_first_impl(const PairCall& c);
 
 extern "C" int vm_conv3x3_pair_first_mid_nhwc(const vm_tensor* x, const void* packed1, int cin1, const float* bias1,
                                               const void* packed2, int cout2, const float* bias2, const float* scale2,
@@ -6066,15 +5888,15 @@ extern "C" int vm_conv3x3_pair_first_mid_nhwc(const vm_tensor* x, const void* pa
   if (!valid_tensor(mid) || mid->dtype != VM_BF16 || mid->c != 64 || !x || mid->n != x->n || mid->h != x->h ||
       mid->w != x->w || reinterpret_cast<uintptr_t>(mid->ptr) % 16 || mid->cstride % 8 || mid->coff % 8)
     return fail(VM_EINVAL, "conv3x3_pair_first_mid: mid must be a 16-byte aligned bf16 [n,h,w,64] view");
-  return pair_first_impl(x, packed1, cin1, bias1, packed2, cout2, bias2, scale2, shift2, act2, y, ypool, nullptr, 0, 0,
-                         nullptr, 1, stream, mid);
+  PairCall c{x, packed1, cin1, bias1, packed2, cout2, bias2, scale2, shift2, act2, y, ypool, stream};
+  c.mid = mid;
+  return pair_first_impl(c);
 }
 
 extern "C" int vm_conv3x3_pair_first_nhwc(const vm_tensor* x, const void* packed1, int cin1, const float* bias1,
                                           const void* packed2, int cout2, const float* bias2, const float* scale2,
                                           const float* shift2, int act2, vm_tensor* y, vm_tensor* ypool, void* stream) {
-  return pair_first_impl(x, packed1, cin1, bias1, packed2, cout2, bias2, scale2, shift2, act2, y, ypool, nullptr, 0, 0,
-                         nullptr, 1, stream);
+  return pair_first_impl({x, packed1, cin1, bias1, packed2, cout2, bias2, scale2, shift2, act2, y, ypool, stream});
 }
 
 extern "C" int vm_conv3x3_pair_first_head_nhwc(const vm_tensor* x, const void* packed1, int cin1, const float* bias1,
@@ -6085,22 +5907,31 @@ extern "C" int vm_conv3x3_pair_first_head_nhwc(const vm_tensor* x, const void* p
   if (!head_w || !partial || head_cin <= 0 || head_coff < 0 || head_coff + cout2 > head_cin)
     return fail(VM_EINVAL, "conv3x3_pair_first_head: head filter [3,3,%d,1] with the pair's %d channels at %d",
                 head_cin, cout2, head_coff);
-  return pair_first_impl(x, packed1, cin1, bias1, packed2, cout2, bias2, scale2, shift2, act2, y, ypool, head_w,
-                         head_cin, head_coff, partial, store_y, stream);
+  PairCall c{x, packed1, cin1, bias1, packed2, cout2, bias2, scale2, shift2, act2, y, ypool, stream};
+  c.head_w = head_w;
+  c.head_cin = head_cin;
+  c.head_coff = head_coff;
+  c.partial = partial;
+  c.store_y = store_y;
+  return pair_first_impl(c);
 }
 
 extern "C" int vm_conv3x3_head_acc_nhwc(const vm_tensor* x, const void* packed, int cin, const float* bias,
                                         const float* y_acc, vm_tensor* y, float* alpha, void* stream) {
   if (!y_acc) return fail(VM_EINVAL, "conv3x3_head_acc: y_acc is NULL");
-  return conv_impl(x, packed, cin, 1, bias, nullptr, nullptr, VM_ACT_NONE, y, nullptr, stream, alpha, 0, 0, nullptr, 0,
-                   nullptr, y_acc);
+  ConvCall c{x, packed, cin, 1, bias, nullptr, nullptr, VM_ACT_NONE, y, stream};
+  c.y2 = alpha;
+  c.y_acc = y_acc;
+  return conv_impl(c);
 }
 
 extern "C" int vm_conv3x3_head_acc_ex_nhwc(const vm_tensor* x, const void* packed, int cin, const float* bias,
                                            const float* scale, const float* shift, const float* y_acc, vm_tensor* y,
                                            float* alpha, void* stream) {
-  return conv_impl(x, packed, cin, 1, bias, scale, shift, VM_ACT_NONE, y, nullptr, stream, alpha, 0, 0, nullptr, 0,
-                   nullptr, y_acc);
+  ConvCall c{x, packed, cin, 1, bias, scale, shift, VM_ACT_NONE, y, stream};
+  c.y2 = alpha;
+  c.y_acc = y_acc;
+  return conv_impl(c);
 }
 
 
@@ -6120,27 +5951,34 @@ extern "C" int vm_conv3x3_split3_nhwc(const vm_tensor* x, const void* packed, in
         ypool->w != (y->w + 1) / 2 || ypool->c != cout)
       return fail(VM_EINVAL, "conv3x3_split3: pool view must be [n, ceil(h/2), ceil(w/2), cout] in the split layout");
   }
-  return conv_impl(x, packed, cin, cout, bias, scale, shift, act, y, ypool, stream, nullptr, 0, 0, work, work_bytes,
-                   nullptr, nullptr, &so);
+  ConvCall c{x, packed, cin, cout, bias, scale, shift, act, y, stream};
+  c.yp = ypool;
+  c.work = work;
+  c.work_bytes = work_bytes;
+  c.so = &so;
+  return conv_impl(c);
 }
 
 extern "C" int vm_conv3x3_head_partial_nhwc(const vm_tensor* x, const void* packed, int cin, const float* bias,
                                             const float* scale, const float* shift, int act, vm_tensor* y,
                                             float* alpha, const float* partial, void* stream) {
   if (!partial) return fail(VM_EINVAL, "conv3x3_head_partial: partial is NULL");
-  return conv_impl(x, packed, cin, 1, bias, scale, shift, act, y, nullptr, stream, alpha, 0, 0, nullptr, 0, partial);
+  ConvCall c{x, packed, cin, 1, bias, scale, shift, act, y, stream};
+  c.y2 = alpha;
+  c.head_part = partial;
+  return conv_impl(c);
 }
 
-static int pair_first_impl(const vm_tensor* x, const void* packed1, int cin1, const float* bias1, const void* packed2,
-                           int cout2, const float* bias2, const float* scale2, const float* shift2, int act2,
-                           vm_tensor* y, vm_tensor* ypool, const float* head_w, int head_cin, int head_coff,
-                           float* partial, int store_y, void* stream, vm_tensor* mid) {
-  if (!valid_tensor(x) || !valid_tensor(y) || !packed1 || !packed2)
+static int pair_first_impl(const PairCall& c) {
+  const vm_tensor* x = c.x;
+  vm_tensor *y = c.y, *ypool = c.ypool;
+  const int cin1 = c.cin1, cout2 = c.cout2;
+  if (!valid_tensor(x) || !valid_tensor(y) || !c.packed1 || !c.packed2)
     return fail(VM_EINVAL, "conv3x3_pair_first: invalid tensor/weights");
   if (cin1 <= 0 || cin1 > 8 || x->c != cin1 || cout2 <= 0 || y->c != cout2)
     return fail(VM_EINVAL, "conv3x3_pair_first: x.c=%d cin1=%d (<= 8) y.c=%d cout2=%d", x->c, cin1, y->c, cout2);
   if (x->n != y->n || x->h != y->h || x->w != y->w) return fail(VM_EINVAL, "conv3x3_pair_first: spatial mismatch");
-  if (act2 < VM_ACT_NONE || act2 > VM_ACT_SOFTMAX) return fail(VM_EINVAL, "conv3x3_pair_first: act %d", act2);
+  if (c.act2 < VM_ACT_NONE || c.act2 > VM_ACT_SOFTMAX) return fail(VM_EINVAL, "conv3x3_pair_first: act %d", c.act2);
   if (ypool && (!valid_tensor(ypool) || ypool->n != y->n || ypool->h != (y->h + 1) / 2 || ypool->w != (y->w + 1) / 2 ||
                 ypool->c != cout2 || ypool->dtype != y->dtype))
     return fail(VM_EINVAL, "conv3x3_pair_first: pool output must be [n, ceil(h/2), ceil(w/2), cout2]");
@@ -6150,43 +5988,43 @@ static int pair_first_impl(const vm_tensor* x, const void* packed1, int cin1, co
   const bool yvec = reinterpret_cast<uintptr_t>(y->ptr) % 16 == 0 && y->cstride % 8 == 0 && y->coff % 8 == 0;
   const bool pvec = !ypool || (reinterpret_cast<uintptr_t>(ypool->ptr) % 16 == 0 && ypool->cstride % 8 == 0 &&
                                ypool->coff % 8 == 0);
-  if (y->dtype != VM_BF16 || !xvec || !yvec || !pvec || cout2 % 8 || act2 == VM_ACT_SOFTMAX || g_conv_kernel == 1 ||
-      g_conv_kernel == 2)
+  if (y->dtype != VM_BF16 || !xvec || !yvec || !pvec || cout2 % 8 || c.act2 == VM_ACT_SOFTMAX || g_opt.conv_kernel == 1 ||
+      g_opt.conv_kernel == 2)
     return fail(VM_EUNSUPPORTED, "conv3x3_pair_first: needs a bf16 output and 16-byte channel views (bf16 x: "
                                  "8-channel pixels)");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
   ConvArgs a{};
   a.x = x->ptr; a.x_cstride = x->cstride; a.x_coff = x->coff; a.H = x->h; a.W = x->w;
   a.M = (long)x->n * x->h * x->w;
   fill_geom(a, geom(64, cout2, VM_BF16));
-  a.w = packed2; a.cout = cout2;
-  a.bias = bias2; a.scale = scale2; a.shift = shift2; a.act = act2;
+  a.w = c.packed2; a.cout = cout2;
+  a.bias = c.bias2; a.scale = c.scale2; a.shift = c.shift2; a.act = c.act2;
   a.y = y->ptr; a.y_cstride = y->cstride; a.y_coff = y->coff; a.y_dtype = y->dtype; a.y_vec = 1;
-  a.w1 = packed1; a.bias1 = bias1; a.x_f32 = xf32; a.x_c = cin1;
+  a.w1 = c.packed1; a.bias1 = c.bias1; a.x_f32 = xf32; a.x_c = cin1;
   if (ypool) { a.py = ypool->ptr; a.py_cstride = ypool->cstride; a.py_coff = ypool->coff; }
   const long sp = (long)x->n * ((x->h + 7) / 8) * ((x->w + 31) / 32);
-  if (partial) {
-    a.hd = partial; a.hw = head_w; a.hw_cin = head_cin; a.hw_coff = head_coff; a.y_skip = store_y ? 0 : 1;
+  if (c.partial) {
+    a.hd = c.partial; a.hw = c.head_w; a.hw_cin = c.head_cin; a.hw_coff = c.head_coff; a.y_skip = c.store_y ? 0 : 1;
   }
   // the strip kernel addresses one image's output / pool with 32-bit byte offsets
   const bool strip_fits = (long)x->h * x->w * y->cstride * 2 < 0x7ffffff0L &&
                           (!ypool || (long)ypool->h * ypool->w * ypool->cstride * 2 < 0x7ffffff0L);
-  if (mid) {  // conv1_1's output too: the strip kernel only (the caller otherwise runs the two convs)
-    if (!(g_pair_strip && g_pair_kernel == 0 && strip_fits && pair_strip_ok(a) &&
-          (long)mid->h * mid->w * mid->cstride * 2 < 0x7ffffff0L))
+  if (c.mid) {  // conv1_1's output too: the strip kernel only (the caller otherwise runs the two convs)
+    if (!(g_opt.pair_strip && g_opt.pair_kernel == 0 && strip_fits && pair_strip_ok(a) &&
+          (long)c.mid->h * c.mid->w * c.mid->cstride * 2 < 0x7ffffff0L))
       return fail(VM_EUNSUPPORTED, "conv3x3_pair_first_mid: needs the strip pair kernel");
-    a.y1 = mid->ptr; a.y1_cstride = mid->cstride; a.y1_coff = mid->coff;
+    a.y1 = c.mid->ptr; a.y1_cstride = c.mid->cstride; a.y1_coff = c.mid->coff;
   }
-  if (g_pair_strip && g_pair_kernel == 0 && strip_fits && pair_strip_ok(a)) return launch_pair_strip(a, x->n, st);
-  if (partial) {  // the head split lives in the persistent pair kernel only
-    if (cout2 != 64 || g_pair_kernel != 0 || sp > 0x7fffffffL)
+  if (g_opt.pair_strip && g_opt.pair_kernel == 0 && strip_fits && pair_strip_ok(a)) return launch_pair_strip(a, x->n, st);
+  if (c.partial) {  // the head split lives in the persistent pair kernel only
+    if (cout2 != 64 || g_opt.pair_kernel != 0 || sp > 0x7fffffffL)
       return fail(VM_EUNSUPPORTED, "conv3x3_pair_first_head: needs the persistent pair kernel (cout2 64)");
-    a.hd = partial; a.hw = head_w; a.hw_cin = head_cin; a.hw_coff = head_coff; a.y_skip = store_y ? 0 : 1;
+    a.hd = c.partial; a.hw = c.head_w; a.hw_cin = c.head_cin; a.hw_coff = c.head_coff; a.y_skip = c.store_y ? 0 : 1;
     return launch_pair_persist<0>(a, sp, st);
   }
-  if (cout2 == 64 && (g_pair_kernel == 0 || g_pair_kernel >= 10) && sp <= 0x7fffffffL) {
+  if (cout2 == 64 && (g_opt.pair_kernel == 0 || g_opt.pair_kernel >= 10) && sp <= 0x7fffffffL) {
 #ifdef VM_STUDY
-    switch (g_pair_kernel) {  // >= 10: timing ablations (garbage results), study build only
+    switch (g_opt.pair_kernel) {  // >= 10: timing ablations (garbage results), study build only
       case 11: return launch_pair_persist<1>(a, sp, st);
       case 12: return launch_pair_persist<2>(a, sp, st);
       case 14: return launch_pair_persist<4>(a, sp, st);
@@ -6204,68 +6042,70 @@ static int pair_first_impl(const vm_tensor* x, const void* packed1, int cin1, co
 extern "C" int vm_conv3x3_head_nhwc(const vm_tensor* x, const void* packed, int cin, const float* bias,
                                     const float* scale, const float* shift, int act, vm_tensor* y, float* alpha,
                                     void* stream) {
-  return conv_impl(x, packed, cin, 1, bias, scale, shift, act, y, nullptr, stream, alpha);
+  ConvCall c{x, packed, cin, 1, bias, scale, shift, act, y, stream};
+  c.y2 = alpha;
+  return conv_impl(c);
 }
 
-static int conv_impl(const vm_tensor* x, const void* packed, int cin, int cout, const float* bias, const float* scale,
-                     const float* shift, int act, vm_tensor* y, const vm_tensor* yp, void* stream, float* y2, int nsrc,
-                     long src_stride, void* work, size_t work_bytes, const float* head_part, const float* y_acc,
-                     const SplitOut* so) {
-  if (!valid_tensor(x, true) || !valid_tensor(y, so != nullptr) || !packed)
+static int conv_impl(const ConvCall& c) {
+  const vm_tensor* x = c.x;
+  vm_tensor* y = c.y;
+  const int cin = c.cin, cout = c.cout;
+  if (!valid_tensor(x, true) || !valid_tensor(y, c.so != nullptr) || !c.packed)
     return fail(VM_EINVAL, "conv3x3: invalid tensor/weights");
   // fp16 operands (the split-fp16 forward, vmatting/split3.py): f32 outputs of the patch kernel (any cout % 4 == 0)
   // or the MFMA head (cout == 1, <= 256 channels per call), or (so) the split-fp16 output with its fused pool; no
   // split sources or softmax
   const bool f16 = x->dtype == VM_F16;
-  if (so && (!f16 || y->dtype != VM_F16 || cout == 1))
+  if (c.so && (!f16 || y->dtype != VM_F16 || cout == 1))
     return fail(VM_EINVAL, "conv3x3_split3: fp16 input and fp16 split output views, cout > 1");
-  if (f16 && ((!so && (y->dtype != VM_F32 || yp)) || nsrc > 1 || act == VM_ACT_SOFTMAX || head_part))
+  if (f16 && ((!c.so && (y->dtype != VM_F32 || c.yp)) || c.nsrc > 1 || c.act == VM_ACT_SOFTMAX || c.head_part))
     return fail(VM_EUNSUPPORTED, "conv3x3: fp16 operands need an f32 (or split) output without sources / softmax");
-  if (y_acc && cout != 1) return fail(VM_EINVAL, "conv3x3: an accumulated pre-activation needs cout == 1");
-  if (head_part && cout != 1) return fail(VM_EINVAL, "conv3x3: head partials need cout == 1");
-  int xc = nsrc > 1 ? nsrc * x->c : x->c;  // sources: x is the view of source 0
+  if (c.y_acc && cout != 1) return fail(VM_EINVAL, "conv3x3: an accumulated pre-activation needs cout == 1");
+  if (c.head_part && cout != 1) return fail(VM_EINVAL, "conv3x3: head partials need cout == 1");
+  int xc = c.nsrc > 1 ? c.nsrc * x->c : x->c;  // sources: x is the view of source 0
   // split-fp16 input stored as two slabs [l, h] (x->c = 2S) for a filter over [l, h, h] (cin = 3S): the third slab is
   // read from the second (ConvArgs::xalias)
   int xalias = 0;
-  if (x->dtype == VM_F16 && nsrc <= 1 && 2 * cin == 3 * x->c && x->c % 64 == 0) {
+  if (x->dtype == VM_F16 && c.nsrc <= 1 && 2 * cin == 3 * x->c && x->c % 64 == 0) {
     xalias = x->c / 2;
     xc = cin;
   }
   if (cin <= 0 || cout <= 0 || xc != cin || y->c != cout)
     return fail(VM_EINVAL, "conv3x3: channel mismatch x.c=%d cin=%d y.c=%d cout=%d", xc, cin, y->c, cout);
-  if (nsrc > 1 && (cout == 1 || yp || x->c % (x->dtype == VM_BF16 ? 32 : 16) || src_stride % 8))
+  if (c.nsrc > 1 && (cout == 1 || c.yp || x->c % (x->dtype == VM_BF16 ? 32 : 16) || c.src_stride % 8))
     return fail(VM_EUNSUPPORTED, "conv3x3: split sources need whole 64-byte granules per source (x.c=%d)", x->c);
   if (x->n != y->n || x->h != y->h || x->w != y->w)
     return fail(VM_EINVAL, "conv3x3: spatial mismatch [%d,%d,%d] vs [%d,%d,%d]", x->n, x->h, x->w, y->n, y->h, y->w);
-  if (act < VM_ACT_NONE || act > VM_ACT_SOFTMAX) return fail(VM_EINVAL, "conv3x3: act %d", act);
+  if (c.act < VM_ACT_NONE || c.act > VM_ACT_SOFTMAX) return fail(VM_EINVAL, "conv3x3: act %d", c.act);
   const int dt = x->dtype;
   PackGeom g = geom(cin, cout, dt);
   const int ce = 16 / elem_bytes(dt);
   if (reinterpret_cast<uintptr_t>(x->ptr) % 16 || x->cstride % ce || x->coff % ce ||
-      x->coff + (nsrc > 1 || xalias ? x->c : g.cin_pad) > x->cstride)
+      x->coff + (c.nsrc > 1 || xalias ? x->c : g.cin_pad) > x->cstride)
     return fail(VM_EUNSUPPORTED,
                 "conv3x3: input view must be 16-byte aligned with channel padding to %d (coff=%d cstride=%d)",
                 g.cin_pad, x->coff, x->cstride);
-  if (act == VM_ACT_SOFTMAX && cout > 128) return fail(VM_EUNSUPPORTED, "conv3x3: fused softmax needs cout <= 128");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (c.act == VM_ACT_SOFTMAX && cout > 128) return fail(VM_EUNSUPPORTED, "conv3x3: fused softmax needs cout <= 128");
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
   const long M = (long)x->n * x->h * x->w;
-  if (yp && cout == 1) return fail(VM_EUNSUPPORTED, "conv3x3_pool: no fused pooling for cout == 1");
+  if (c.yp && cout == 1) return fail(VM_EUNSUPPORTED, "conv3x3_pool: no fused pooling for cout == 1");
 
   if (cout == 1) {
     HeadArgs h{};
     h.x = x->ptr; h.x_cstride = x->cstride; h.x_coff = x->coff; h.H = x->h; h.W = x->w; h.M = M;
     h.cin_pad = g.cin_pad; h.K9 = g.K9; h.K_pad = g.K_pad; h.chunk_major = g.chunk_major; h.ng = g.ng;
-    h.w = packed; h.bias = bias; h.scale = scale; h.shift = shift; h.act = act;
-    h.y = y->ptr; h.y_cstride = y->cstride; h.y_coff = y->coff; h.y_dtype = y->dtype; h.y2 = y2;
-    h.part = head_part;
-    h.yacc = y_acc;
+    h.w = c.packed; h.bias = c.bias; h.scale = c.scale; h.shift = c.shift; h.act = c.act;
+    h.y = y->ptr; h.y_cstride = y->cstride; h.y_coff = y->coff; h.y_dtype = y->dtype; h.y2 = c.y2;
+    h.part = c.head_part;
+    h.yacc = c.y_acc;
     const int nks = (g.cin_pad + 4 * ce - 1) / (4 * ce);
     // the split-fp16 x3 head over a two-slab [l, h] view of 128-channel slabs (cin 384 as [l, h, h]): one call
-    if (f16 && xalias == 128 && nks == 12 && g_head_kernel == 0) {
+    if (f16 && xalias == 128 && nks == 12 && g_opt.head_kernel == 0) {
       // 16-row tiles: an 18 x 66 input window per 16 x 64 outputs (1.16x the tile's pixels, 1.29x for 8 rows); the
       // per-pixel tap sums and the 9-tap epilogue are the same arithmetic whatever the tile: bit-identical
       constexpr int TW = 64;
-      const int th16 = g_head_th == 16 ? 16 : 8;
+      const int th16 = g_opt.head_th == 16 ? 16 : 8;
       const long tiles = (long)x->n * ((x->h + th16 - 1) / th16) * ((x->w + TW - 1) / TW);
       if (tiles > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3 head: too many tiles");
       snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_head_mfma<vm::f16_t, %d, %d, 12, true>", th16, TW);
@@ -6277,14 +6117,14 @@ static int conv_impl(const vm_tensor* x, const void* packed, int cin, int cout, 
                            (size_t)9 * g.cin_pad * 2, st, h);
       return check_launch("conv3x3_head_mfma");
     }
-    if ((head_part || y_acc || f16) && (g_head_kernel != 0 || nks > 8))
+    if ((c.head_part || c.y_acc || f16) && (g_opt.head_kernel != 0 || nks > 8))
       return fail(VM_EUNSUPPORTED, "conv3x3 head: partials / accumulation / fp16 need the MFMA head kernel (cin <= 256, "
                                    "or 384 as a two-slab split-fp16 view)");
-    if (g_head_kernel == 0 && nks <= 8) {
+    if (g_opt.head_kernel == 0 && nks <= 8) {
       constexpr int TW = 64;
       // 16-row tiles for the bf16 128-channel head (cat1 of UNetVideo): input window 18 x 66 per 16 x 64 outputs
       // (1.16x the tile's bytes instead of 1.29x for 8 rows)
-      const int TH = (dt == VM_BF16 && (nks == 4 || (nks == 2 && head_part)) && g_head_th == 16) ? 16 : 8;
+      const int TH = (dt == VM_BF16 && (nks == 4 || (nks == 2 && c.head_part)) && g_opt.head_th == 16) ? 16 : 8;
       const long tiles = (long)x->n * ((x->h + TH - 1) / TH) * ((x->w + TW - 1) / TW);
       if (tiles > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3 head: too many tiles");
       const size_t lds = (size_t)9 * g.cin_pad * elem_bytes(dt);
@@ -6313,7 +6153,7 @@ static int conv_impl(const vm_tensor* x, const void* packed, int cin, int cout, 
     }
     constexpr int P = 8;
     const int nch = g.cin_pad / (16 * ce);
-    if ((nch == 1 || nch == 2) && g.cin_pad % (16 * ce) == 0 && g_head_kernel != 1) {
+    if ((nch == 1 || nch == 2) && g.cin_pad % (16 * ce) == 0 && g_opt.head_kernel != 1) {
       const long strips = (M / x->w) * ((x->w + P - 1) / P);
       const int grid = grid_for((strips + 15) / 16, 1, 256 * 8);
       const size_t lds = (size_t)9 * g.cin_pad * elem_bytes(dt);
@@ -6339,23 +6179,23 @@ static int conv_impl(const vm_tensor* x, const void* packed, int cin, int cout, 
   ConvArgs a{};
   a.x = x->ptr; a.x_cstride = x->cstride; a.x_coff = x->coff; a.H = x->h; a.W = x->w; a.M = M;
   fill_geom(a, g);
-  if (nsrc > 1) {
+  if (c.nsrc > 1) {
     a.x_src_c = x->c;
-    a.x_src_stride = src_stride;
+    a.x_src_stride = c.src_stride;
   }
   a.ksplit = 1;
-  a.w = packed; a.cout = cout;
-  a.bias = bias; a.scale = scale; a.shift = shift; a.act = act;
+  a.w = c.packed; a.cout = cout;
+  a.bias = c.bias; a.scale = c.scale; a.shift = c.shift; a.act = c.act;
   a.y = y->ptr; a.y_cstride = y->cstride; a.y_coff = y->coff; a.y_dtype = y->dtype;
   const int yve = 16 / elem_bytes(y->dtype);
   a.y_vec = (reinterpret_cast<uintptr_t>(y->ptr) % 16 == 0) && (y->cstride % yve == 0) && (y->coff % yve == 0);
-  if (yp && !f16) {
-    const bool pvec = reinterpret_cast<uintptr_t>(yp->ptr) % 16 == 0 && yp->cstride % 8 == 0 && yp->coff % 8 == 0;
-    if (cout == 1 || dt != VM_BF16 || !pvec || !patch_ok(a, 2) || g_conv_kernel == 1 || g_conv_kernel == 2)
+  if (c.yp && !f16) {
+    const bool pvec = reinterpret_cast<uintptr_t>(c.yp->ptr) % 16 == 0 && c.yp->cstride % 8 == 0 && c.yp->coff % 8 == 0;
+    if (cout == 1 || dt != VM_BF16 || !pvec || !patch_ok(a, 2) || g_opt.conv_kernel == 1 || g_opt.conv_kernel == 2)
       return fail(VM_EUNSUPPORTED, "conv3x3_pool: fused pooling needs the bf16 patch kernel");
-    a.py = yp->ptr;
-    a.py_cstride = yp->cstride;
-    a.py_coff = yp->coff;
+    a.py = c.yp->ptr;
+    a.py_cstride = c.yp->cstride;
+    a.py_coff = c.yp->coff;
     return dispatch_patch(a, st);
   }
   if (f16) {  // the patch kernel's fp16 form (+ split-K on small grids with a workspace)
@@ -6363,54 +6203,54 @@ static int conv_impl(const vm_tensor* x, const void* packed, int cin, int cout, 
     a.xalias = xalias;
     a.py = nullptr;
     a.up = 0;
-    if (so) {  // split output: staged like an f32 output, stored as fp16 slabs (y_cstride stays in fp16 elements)
+    if (c.so) {  // split output: staged like an f32 output, stored as fp16 slabs (y_cstride stays in fp16 elements)
       a.y_dtype = VM_F32;
       a.y_vec = 1;
-      a.ysplit = so->yslab;
-      a.ovf = so->ovf;
-      if (yp) {
-        a.py = yp->ptr;
-        a.py_cstride = yp->cstride;
-        a.py_coff = yp->coff;
-        a.psplit = so->pslab;
+      a.ysplit = c.so->yslab;
+      a.ovf = c.so->ovf;
+      if (c.yp) {
+        a.py = c.yp->ptr;
+        a.py_cstride = c.yp->cstride;
+        a.py_coff = c.yp->coff;
+        a.psplit = c.so->pslab;
       }
     }
     if (!patch_ok(a, 2)) return fail(VM_EUNSUPPORTED, "conv3x3: fp16 operands need the patch kernel (cin %% 32 == 0)");
-    if (work && (cout & 3) == 0 && !yp) {
+    if (c.work && (cout & 3) == 0 && !c.yp) {
       const int ks = splitk_plan(x->n, x->h, x->w, a.cin_pad, cout);
-      if (ks > 1 && work_bytes >= (size_t)ks * M * cout * sizeof(float)) {
+      if (ks > 1 && c.work_bytes >= (size_t)ks * M * cout * sizeof(float)) {
         a.ksplit = ks;
-        a.part = reinterpret_cast<float*>(work);
+        a.part = reinterpret_cast<float*>(c.work);
       }
     }
     return dispatch_patch(a, st);
   }
-  if (g_conv_kernel == 0 && thin_ok(dt, g, cout, a.x_src_c, act, x)) {
-    const int ks = work ? thin_splitk_plan(x->n, x->h, x->w, a.cin_pad) : 1;
-    if (ks > 1 && work_bytes >= (size_t)ks * M * cout * sizeof(float)) {
+  if (g_opt.conv_kernel == 0 && thin_ok(dt, g, cout, a.x_src_c, c.act, x)) {
+    const int ks = c.work ? thin_splitk_plan(x->n, x->h, x->w, a.cin_pad) : 1;
+    if (ks > 1 && c.work_bytes >= (size_t)ks * M * cout * sizeof(float)) {
       a.ksplit = ks;
-      a.part = reinterpret_cast<float*>(work);
+      a.part = reinterpret_cast<float*>(c.work);
     }
     return dispatch_thin(a, x->n, st);
   }
-  if (nsrc > 1) {
+  if (c.nsrc > 1) {
     // the patch / row-stationary / generic kernels add source s's offset (s * src_stride elements) into 32-bit
     // byte offsets inside one image's buffer resource: the whole span must stay below it (the thin kernel above
     // forms 64-bit source pointers).  Callers materialise the concat instead (ops.conv3x3)
-    const long span = ((long)(nsrc - 1) * src_stride + (long)x->h * x->w * x->cstride) * elem_bytes(dt);
-    if (span >= g_src_span_limit)
+    const long span = ((long)(c.nsrc - 1) * c.src_stride + (long)x->h * x->w * x->cstride) * elem_bytes(dt);
+    if (span >= g_opt.src_span_limit)
       return fail(VM_EUNSUPPORTED, "conv3x3: split sources span %ld bytes (limit %ld): materialise the concat", span,
-                  g_src_span_limit);
+                  g_opt.src_span_limit);
   }
-  if (dt == VM_BF16 && work && g_conv_kernel == 0 && patch_ok(a, 2) && (cout & 3) == 0) {
+  if (dt == VM_BF16 && c.work && g_opt.conv_kernel == 0 && patch_ok(a, 2) && (cout & 3) == 0) {
     const int ks = splitk_plan(x->n, x->h, x->w, a.cin_pad, cout);
-    if (ks > 1 && work_bytes >= (size_t)ks * M * cout * sizeof(float)) {
+    if (ks > 1 && c.work_bytes >= (size_t)ks * M * cout * sizeof(float)) {
       a.ksplit = ks;
-      a.part = reinterpret_cast<float*>(work);
+      a.part = reinterpret_cast<float*>(c.work);
       return dispatch_patch(a, st);
     }
   }
-  if (dt == VM_BF16 && g_conv_kernel == 0 && narrowin_ok(a, g, cout, act, x, y)) return launch_narrowin(a, x->n, g, st);
+  if (dt == VM_BF16 && g_opt.conv_kernel == 0 && narrowin_ok(a, g, cout, c.act, x, y)) return launch_narrowin(a, x->n, g, st);
   if (dt == VM_BF16) return dispatch_mfma<uint16_t>(a, st);
   return dispatch_mfma<float>(a, st, cin);
 }
@@ -6419,7 +6259,7 @@ static int conv_impl(const vm_tensor* x, const void* packed, int cin, int cout, 
 extern "C" size_t vm_conv3x3_workspace_bytes(const vm_tensor* x, int cin, int cout) {
   if (!x || (x->dtype != VM_BF16 && x->dtype != VM_F16) || cin <= 0 || cout <= 0) return 0;
   const PackGeom g = geom(cin, cout, VM_BF16);
-  if (x->dtype == VM_BF16 && g_conv_kernel == 0 && thin_ok(VM_BF16, g, cout, cin == x->c ? 0 : x->c, VM_ACT_NONE, x)) {
+  if (x->dtype == VM_BF16 && g_opt.conv_kernel == 0 && thin_ok(VM_BF16, g, cout, cin == x->c ? 0 : x->c, VM_ACT_NONE, x)) {
     const int ks = thin_splitk_plan(x->n, x->h, x->w, g.cin_pad);
     return ks > 1 ? (size_t)ks * x->n * x->h * x->w * cout * sizeof(float) : 0;
   }
@@ -6434,6 +6274,10 @@ extern "C" int vm_conv3x3_ex_nhwc(const vm_tensor* x, int nsrc, long src_stride,
                                   void* work, size_t work_bytes, void* stream) {
   if (nsrc < 0 || (nsrc > 1 && src_stride <= 0)) return fail(VM_EINVAL, "conv3x3_ex: nsrc %d stride %ld", nsrc,
                                                             src_stride);
-  return conv_impl(x, packed, cin, cout, bias, scale, shift, act, y, nullptr, stream, nullptr, nsrc, src_stride, work,
-                   work_bytes);
+  ConvCall c{x, packed, cin, cout, bias, scale, shift, act, y, stream};
+  c.nsrc = nsrc;
+  c.src_stride = src_stride;
+  c.work = work;
+  c.work_bytes = work_bytes;
+  return conv_impl(c);
 }

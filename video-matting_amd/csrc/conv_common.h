@@ -1,4 +1,5 @@
-// Conv argument block and device helpers shared by the 3x3 conv kernels (conv3x3.hip, conv_rows.hip).
+// Conv argument block and device helpers shared by the 3x3 conv kernels (conv3x3.hip, conv_rows.hip, conv_pair.hip)
+// and train.hip's MFMA kernels.  Device code only: the host side (options, launchers) is conv_dispatch.h.
 #pragma once
 
 #include <type_traits>
@@ -240,17 +241,6 @@ __device__ __forceinline__ uint4 chunk_pair(uint2 lo, uint2 hi) {
   return make_uint4(sx[0], sy[0], sx[1], sy[1]);
 }
 
-// name of the kernel the last conv call on this thread launched, spelled as rocprofv3 reports it (conv3x3.hip)
-extern thread_local char g_last_kernel[128];
-
-// vm_set_option "conv_prio": ConvArgs::prio for the 8-wave conv kernels (patch, persistent patch, row-stationary)
-extern long g_conv_prio;
-// launchers defined in conv_rows.hip (called from conv3x3.hip's dispatch)
-bool rows_ok(const ConvArgs& a);
-int launch_rows(ConvArgs& a, hipStream_t st, int cfg);
-// launchers defined in conv_pair.hip
-bool pair_strip_ok(const ConvArgs& a);
-int launch_pair_strip(ConvArgs& a, long nimg, hipStream_t st);
-extern long g_pair_strip_abl, g_pair_strip_pin;
+// (the options, the launchers of conv_rows.hip / conv_pair.hip and g_last_kernel: conv_dispatch.h)
 
 }  // namespace vm

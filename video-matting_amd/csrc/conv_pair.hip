@@ -19,7 +19,7 @@
 // Every MFMA sequence (conv1_1: 3 K-steps of 4 taps x 8 channels; conv1_2: granule 0 taps 0..8, granule 1 taps
 // 0..8; head: channels 0..31 then 32..63) is the one the tile kernels run, so outputs, pool and partials are
 // bit-identical to conv3x3_pair_persist (tests/test_gpu_parity.py::test_pair_strip_*).
-#include "conv_common.h"
+#include "conv_dispatch.h"
 
 namespace vm {
 
@@ -455,15 +455,10 @@ bool pair_strip_ok(const ConvArgs& a) {
          imgb >= 2048 && a.W > 0 && a.H > 0 && (long)a.H * a.W < (1L << 24);
 }
 
-long g_pair_strip_abl = 0;  // study build: timing-only ablations (1 no conv1_1 MFMAs, 2 no conv1_2 MFMAs, 4 no row
-                            // barrier, 8 no input DMA, 16 no conv1_2 epilogue; garbage results)
-
-long g_pair_strip_pin = 1;  // 1: conv1_2's LDS reads pinned 2 ahead of its MFMAs; 0: left to the scheduler (A/B)
-
 template <int ACT, int ABL, int PIN = 1>
 static void launch_strip_act(ConvArgs& a, long grid, int seg, int nseg, int nstrip, hipStream_t st) {
   if constexpr (PIN) {
-    if (!g_pair_strip_pin) return launch_strip_act<ACT, ABL, 0>(a, grid, seg, nseg, nstrip, st);
+    if (!g_opt.pair_strip_pin) return launch_strip_act<ACT, ABL, 0>(a, grid, seg, nseg, nstrip, st);
   }
   if (a.x_f32 && a.x_c == 7)
     hipLaunchKernelGGL((conv3x3_pair_strip<2, ACT, ABL, PIN, 7>), dim3((unsigned)grid), dim3(128), StripCfg::LDS, st, a,
@@ -502,7 +497,7 @@ int launch_pair_strip(ConvArgs& a, long nimg, hipStream_t st) {
   if (grid > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3_pair_strip: grid too large");
   snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_pair_strip");
 #ifdef VM_STUDY
-  switch (g_pair_strip_abl) {
+  switch (g_opt.pair_strip_abl) {
     case 1: launch_strip_abl<1>(a, grid, seg, (int)nseg, nstrip, st); return check_launch("abl");
     case 2: launch_strip_abl<2>(a, grid, seg, (int)nseg, nstrip, st); return check_launch("abl");
     case 3: launch_strip_abl<3>(a, grid, seg, (int)nseg, nstrip, st); return check_launch("abl");

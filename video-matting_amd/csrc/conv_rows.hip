@@ -27,7 +27,7 @@
 // lane exchange), so a tile change costs no LDS round trip, no block-wide barrier and no DMA latency.
 #include <type_traits>
 
-#include "conv_common.h"
+#include "conv_dispatch.h"
 
 namespace vm {
 
@@ -582,7 +582,7 @@ static int launch_th(ConvArgs& a, hipStream_t st) {
   a.tiles_n = (a.cout + C::BN - 1) / C::BN;
   if (sp * a.tiles_n > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3: too many tiles");
   a.tiles_total = (int)(sp * a.tiles_n);
-  a.prio = (int)g_conv_prio;
+  a.prio = (int)g_opt.conv_prio;
   // persistent: one block per CU (LDS-limited), a multiple of 8 so every XCD gets the same number of blocks
   long grid = g_num_cu < a.tiles_total ? g_num_cu : a.tiles_total;
   grid = (grid + 7) / 8 * 8;

@@ -518,6 +518,13 @@ __global__ __launch_bounds__(256) void bn_apply8_kernel(const TX* x, int xcs, TY
 // occupancy), unlike the backward's (train.hip bn_bwd_partial8 / apply8: -2 %)
 long g_bn_vec_fwd = 0;
 
+// this file's vm_set_option keys (vm_common.h OptDef)
+const OptDef bn_options[] = {
+    {"bn_vec_fwd", &g_bn_vec_fwd, OPT_ANY},
+    {"bn_blocks", &g_bn_target, OPT_RANGE, 2, {1, BN_TARGET_MAX}},
+    {nullptr},
+};
+
 static bool vec8_view(const vm_tensor* t) {
   return t->cstride % 8 == 0 && t->coff % 8 == 0 && reinterpret_cast<uintptr_t>(t->ptr) % 16 == 0 && t->c % 8 == 0 &&
          t->c <= 512;

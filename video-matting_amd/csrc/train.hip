@@ -2366,65 +2366,24 @@ static int launch_wgrad_taps_dma(WgArgs& a, float* dw, hipStream_t st) {
 }
 }  // namespace trn
 
-int train_set_option(const char* key, long value) {
-  if (!strcmp(key, "wgrad_reduce4")) {
-    trn::g_wgrad_reduce4 = value;
-    return 1;
-  }
-  if (!strcmp(key, "wgrad_variant")) {
-    trn::g_wgrad_variant = value;
-    return 1;
-  }
-  if (!strcmp(key, "wgrad_taps")) {
-    trn::g_wgrad_taps = value;
-    return 1;
-  }
-  if (!strcmp(key, "wgrad_dma")) {
-    trn::g_wgrad_dma = value;
-    return 1;
-  }
-  if (!strcmp(key, "bn_vec")) {
-    trn::g_bn_vec = value;
-    return 1;
-  }
-  if (!strcmp(key, "relu_bias_vec")) {
-    trn::g_relu_bias_vec = value;
-    return 1;
-  }
-  if (!strcmp(key, "resize_bwd_2x")) {
-    trn::g_resize_bwd_2x = value;
-    return 1;
-  }
-  if (!strcmp(key, "relu_bias_iters")) {
-    trn::g_relu_bias_iters = value;
-    return 1;
-  }
-  if (!strcmp(key, "wgrad_mfma_pipe")) {
-    trn::g_wgrad_mfma_pipe = value;
-    return 1;
-  }
-  if (!strcmp(key, "wgrad_wide_pipe")) {
-    trn::g_wgrad_wide_pipe = value;
-    return 1;
-  }
-  if (!strcmp(key, "wgrad_wide_target")) {  // (<= WW_TARGET_BLOCKS: the workspace query's bound)
-    trn::g_wgrad_wide_target = value;
-    return 1;
-  }
-  if (!strcmp(key, "wgrad_wide_cs")) {
-    trn::g_wgrad_wide_cs = value;
-    return 1;
-  }
-  if (!strcmp(key, "wgrad_wide_dbuf")) {
-    trn::g_wgrad_wide_dbuf = value;
-    return 1;
-  }
-  if (!strcmp(key, "wgrad_dma_cfg")) {
-    trn::g_wgrad_dma_cfg = value;
-    return 1;
-  }
-  return 0;
-}
+// this file's vm_set_option keys (vm_common.h OptDef): every one takes any value
+const OptDef train_options[] = {
+    {"wgrad_reduce4", &trn::g_wgrad_reduce4, OPT_ANY},
+    {"wgrad_variant", &trn::g_wgrad_variant, OPT_ANY},
+    {"wgrad_taps", &trn::g_wgrad_taps, OPT_ANY},
+    {"wgrad_dma", &trn::g_wgrad_dma, OPT_ANY},
+    {"bn_vec", &trn::g_bn_vec, OPT_ANY},
+    {"relu_bias_vec", &trn::g_relu_bias_vec, OPT_ANY},
+    {"resize_bwd_2x", &trn::g_resize_bwd_2x, OPT_ANY},
+    {"relu_bias_iters", &trn::g_relu_bias_iters, OPT_ANY},
+    {"wgrad_mfma_pipe", &trn::g_wgrad_mfma_pipe, OPT_ANY},
+    {"wgrad_wide_pipe", &trn::g_wgrad_wide_pipe, OPT_ANY},
+    {"wgrad_wide_target", &trn::g_wgrad_wide_target, OPT_ANY},  // (<= WW_TARGET_BLOCKS: the workspace query's bound)
+    {"wgrad_wide_cs", &trn::g_wgrad_wide_cs, OPT_ANY},
+    {"wgrad_wide_dbuf", &trn::g_wgrad_wide_dbuf, OPT_ANY},
+    {"wgrad_dma_cfg", &trn::g_wgrad_dma_cfg, OPT_ANY},
+    {nullptr},
+};
 
 namespace trn {
 

@@ -14,8 +14,23 @@ namespace vm {
 // per-thread error text for vm_last_error()
 void set_error(const char* fmt, ...);
 
-// tuning knobs of the training kernels (train.hip), reached through vm_set_option: 1 = handled, 0 = unknown key
-int train_set_option(const char* key, long value);
+// One vm_set_option key: where its value lives and which values it takes.  The files that own options each define a
+// table of these, ended by a null key (conv_options in conv3x3.hip, train_options in train.hip, bn_options in
+// elementwise.hip); vm_set_option walks the three.
+enum OptKind {
+  OPT_ANY,    // every value
+  OPT_RANGE,  // v[0] <= value <= v[1]
+  OPT_SET,    // one of v[0 .. n)
+};
+struct OptDef {
+  const char* key;
+  long* value;
+  OptKind kind;
+  int n;
+  long v[5];
+  const char* note;  // appended to the rejection message (may be null)
+};
+extern const OptDef train_options[], bn_options[];
 
 inline int fail(int code, const char* fmt, ...) {
   char buf[512];
