@@ -8,7 +8,9 @@ accuracy in three fp16 MFMA products per conv (VERDICT r05 "next" item 2: north_
   goldens        the reference-generated goldens (tests/golden/unet_*_70x90.npz): alpha within 1e-4
   1080p          the bench's timed frame and weights: alpha within 1e-4 of the CPU oracle's f32 forward — north_star's
                  bound — and logits within 1e-5 relative
-  overflow       frames whose activations leave fp16's range set the flag, and build() re-runs them on bf16x6
+  overflow       frames whose activations leave fp16's range set the flag, and build() re-runs them on bf16x6 — also
+                 where the input itself is in range and the overflow starts inside the network, and on a caller's flag
+                 slot (the kernels' own values and flags: test_gpu_split3_epilogues.py)
 """
 
 import numpy as np
@@ -212,6 +214,46 @@ def test_unet_f16x3_overflow_falls_back_to_x6(vgg0):
     assert m.split_mode == "bf16x6"
     r = om.unet_forward(x, m.params, dtype=np.float64)
     lg = H(m.conv1_3)
+    assert np.abs(lg - r["conv1_3"]).max() <= 1e-5 * np.abs(r["conv1_3"]).max()
+
+
+# the layers of oracle.models.unet_forward whose values the f16x3 forward stores split (conv outputs, pools, the
+# [upconv, skip] concats); conv5_2, conv4_4, conv3_4 and conv2_3 stay f32 and reach a split only through their resize
+SPLIT_LAYERS = ("conv1_1", "conv1_2", "pool1", "conv2_1", "conv2_2", "pool2", "conv3_1", "conv3_2", "conv3_3", "pool3",
+                "conv4_1", "conv4_2", "conv4_3", "pool4", "conv5_1", "upconv1", "upconv2", "upconv3", "upconv4")
+
+
+def test_unet_f16x3_mid_network_overflow(vgg0):
+    """Overflow that starts inside the network: a frame whose input is in fp16's range (so the first split3h raises
+    nothing) but whose activations are not — uniform(-1, 1) * 3e4: the float64 oracle puts max |x| at 29999 and the
+    largest split activation at 2.8e5 (conv3_1; conv1_1 already 1.6e5), both asserted here.  forward() reports it
+    through overflowed(), and build() lands on bf16x6 with logits within 1e-5 of the oracle's max."""
+    from vmatting import unet
+    x = np.random.RandomState(3).uniform(-1, 1, (1, 24, 40, 7)).astype(np.float32) * np.float32(3e4)
+    np.random.seed(0)
+    m = unet.UNetVideo(vgg0, dtype="f16x3")
+    m.prepare()
+    r = om.unet_forward(x, m.params, dtype=np.float64)
+    assert np.abs(x).max() < 32760
+    assert max(np.abs(r[k]).max() for k in SPLIT_LAYERS) >= 2 * 65520
+    m.forward(torch.from_numpy(x).to(DEV))
+    assert m.overflowed()
+    assert m.split_mode == "f16x3"  # forward() reports, only build() switches
+    # a forward on a slot of its own reports there and leaves the model's flag alone
+    cool = torch.from_numpy(x / np.float32(250)).to(DEV)
+    slot = torch.ones(3, dtype=torch.int32, device=DEV)
+    m.forward(cool, overflow=slot[1:2])
+    assert slot.tolist() == [1, 0, 1] and m.overflowed()
+    m.forward(cool)
+    assert not m.overflowed()
+    m.forward(torch.from_numpy(x).to(DEV), overflow=slot[1:2])
+    assert slot.tolist() == [1, 1, 1] and not m.overflowed()
+    np.random.seed(0)
+    m = unet.UNetVideo(vgg0, dtype="f16x3")
+    m.build(x)
+    assert m.split_mode == "bf16x6"
+    lg = H(m.conv1_3)
+    assert np.isfinite(H(m.output)).all()
     assert np.abs(lg - r["conv1_3"]).max() <= 1e-5 * np.abs(r["conv1_3"]).max()
 
 

@@ -4,7 +4,10 @@ all-gather) over synthetic 1080p frames, checked frame by frame.
 * bf16: every gathered matte is bit-equal to a standalone single-frame forward() of that frame (the chunked,
   graph-replayed, batched path changes nothing about a frame's arithmetic);
 * fp32: one sampled frame's alpha within 1e-4 max-abs of the numpy f32 oracle (north_star's bound), its logits
-  within 1e-4 of their scale.
+  within 1e-4 of their scale;
+* f16x3: a chunk whose activations leave fp16's range in the middle of a graph-replayed (or eager) multi-chunk run
+  is reported in ``overflowed_chunks`` and re-run on bf16x6; the other chunks' mattes stay bit-equal to standalone
+  f16x3 forwards.
 World 1 here, plus world 2 as two processes sharing the one GPU over gloo (the real model, broadcast, graphs and
 the uneven gather); the sharding / gather arithmetic alone is covered with gloo on CPU in test_host.py.
 """
@@ -53,6 +56,80 @@ def test_video_batch_eager_equals_graph(model_bf16):
     g = video.VideoMatter(model_bf16, frames, chunk=2, graph=True).run().clone()
     e = video.VideoMatter(model_bf16, frames, chunk=2, graph=False).run().clone()
     assert torch.equal(g, e)
+
+
+def test_video_matter_bf16_has_no_flag_slots(model_bf16):
+    """Only an f16x3 model gets range-flag slots (and the host read after run()): the bf16 path is as it was."""
+    from vmatting import video
+    vm = video.VideoMatter(model_bf16, video.synthetic_frames(3, 24, 40), chunk=2, graph=False)
+    vm.run()
+    assert vm._slots is None and vm._x6 is None and vm.overflowed_chunks == []
+    with pytest.raises(ValueError):
+        model_bf16.forward(vm.frames[:1], overflow=torch.zeros(1, dtype=torch.int32, device="cuda"))
+
+
+# layers whose values the f16x3 forward stores split (tests/test_gpu_split3.py SPLIT_LAYERS)
+SPLIT_LAYERS = ("conv1_1", "conv1_2", "pool1", "conv2_1", "conv2_2", "pool2", "conv3_1", "conv3_2", "conv3_3", "pool3",
+                "conv4_1", "conv4_2", "conv4_3", "pool4", "conv5_1", "upconv1", "upconv2", "upconv3", "upconv4")
+HOT = 3  # the hot frame: chunk 1 of the spans (0, 2), (2, 4), (4, 5)
+
+
+@pytest.fixture(scope="module")
+def overflow_video(vgg0):
+    """Five 24 x 40 frames, uniform(-1, 1) * 120 (the float64 oracle's largest activation ~1.1e3) except frame 3 at
+    * 3e4 (input below 32760, activations to 2.8e5), a cool replacement for it, the oracle's forward of each, and the
+    standalone single-frame f16x3 alpha of every cool frame (one model, build() per frame)."""
+    from oracle import models as om
+    from vmatting import unet
+    frames = np.stack([np.random.RandomState(10 + i).uniform(-1, 1, (24, 40, 7)).astype(np.float32) *
+                       np.float32(3e4 if i == HOT else 120.0) for i in range(6)])
+    np.random.seed(0)
+    single = unet.UNetVideo(vgg0, dtype="f16x3", device="cuda")
+    single.prepare()
+    oracle = [om.unet_forward(frames[i:i + 1], single.params, dtype=np.float64) for i in range(6)]
+    alone = {}
+    for i in range(6):
+        if i != HOT:
+            alone[i] = single.build(frames[i:i + 1]).clone()
+            assert single.split_mode == "f16x3"
+    return frames, oracle, alone
+
+
+@pytest.mark.parametrize("graph", [True, False], ids=["graph", "eager"])
+def test_video_f16x3_middle_chunk_overflow_is_reported_and_repaired(overflow_video, vgg0, graph):
+    """A multi-chunk run whose MIDDLE chunk leaves fp16's range: every chunk's forward (captured or eager) zeroes and
+    sets its own flag slot, so the last chunk cannot clear the report (one shared flag did: overflowed() then showed
+    the last chunk only and the hot chunk's inf / NaN alpha went unnoticed); run() re-runs chunk 1 on bf16x6."""
+    from vmatting import unet, video
+    frames, oracle, alone = overflow_video
+    peak = [max(np.abs(r[k]).max() for k in SPLIT_LAYERS) for r in oracle]
+    assert np.abs(frames[HOT]).max() < 32760 and peak[HOT] >= 2 * 65520
+    assert all(peak[i] <= 65520 / 4 for i in range(6) if i != HOT)
+    np.random.seed(0)
+    model = unet.UNetVideo(vgg0, dtype="f16x3", device="cuda")
+    dev = torch.from_numpy(frames[:5]).to("cuda").contiguous()
+    vm = video.VideoMatter(model, dev, chunk=2, graph=graph)
+    assert vm.spans == [(0, 2), (2, 4), (4, 5)]
+    alpha = vm.run().clone()
+    torch.cuda.synchronize()
+    assert vm.overflowed_chunks == [1]
+    assert model.split_mode == "f16x3"
+    assert torch.isfinite(alpha).all()
+    for i in (0, 1, 4):  # untouched chunks: the f16x3 alpha of the frame on its own, bit for bit
+        assert torch.equal(alpha[i], alone[i][0]), "frame %d differs from its standalone f16x3 forward" % i
+    # the re-run chunk (frames 2 and 3): bf16x6 logits within 1e-5 of the oracle's max, alpha written from them
+    lg = vm._x6.logits.cpu().numpy().astype(np.float64)
+    for j, i in enumerate((2, 3)):
+        want = oracle[i]["conv1_3"][0]
+        assert np.abs(lg[j] - want).max() <= 1e-5 * np.abs(want).max(), i
+    assert torch.allclose(alpha[2:4], torch.sigmoid(vm._x6.logits), rtol=0, atol=1e-6)
+    # the hot frame replaced in place by a cool one: the same graphs, no chunk flagged, every frame as on its own
+    dev[HOT].copy_(torch.from_numpy(frames[5]))
+    alpha = vm.run().clone()
+    torch.cuda.synchronize()
+    assert vm.overflowed_chunks == []
+    for i, k in ((0, 0), (1, 1), (2, 2), (3, 5), (4, 4)):
+        assert torch.equal(alpha[i], alone[k][0]), "frame %d differs from its standalone f16x3 forward" % i
 
 
 def test_shape_switch_after_dropped_graph(vgg0):

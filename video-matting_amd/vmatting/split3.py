@@ -15,8 +15,11 @@ whole 1080p forward on the bench's frame and weights (tools/split_emulate.py) pu
 forward (logits 4.0e-7 relative), bf16 x3 7.3e-4.  The filter scale keeps the small parts Wl in fp16's normal range
 (He-normal filters are ~0.01-0.1, so their unscaled low parts would be subnormal); it is a power of two, so the
 epilogue's ``* 2^-t`` is exact (the conv's per-channel scale; the bias rides in the shift).  Activations stay
-unscaled: |x| on this network is ~2e3 against fp16's 65504; a split that meets |x| >= 65520 sets an overflow flag
-(``overflowed()``), and ``UNet.build`` then re-runs the frames on the bf16x6 path.
+unscaled: |x| on this network is ~2e3 against fp16's 65504; every kernel that writes a split activation sets an
+overflow flag where it meets |x| >= 65520.  A forward zeroes and sets one flag slot: the model's own by default
+(``overflowed()``; ``UNet.build`` then re-runs the frames on the bf16x6 path), or the one-element int32 device view
+its caller hands it (``forward(..., overflow=slot)``: video.VideoMatter gives every chunk of a video batch its own
+slot, reads them once after the run and re-runs the flagged chunks on a bf16x6 forward).
 
 Cost: 3x the MFMA work of the bf16 forward (x6: 6x) on the same patch kernels (their fp16 MFMA form,
 v_mfma_f32_16x16x32_f16); the conv's epilogue writes its output split (vm_conv3x3_split3_nhwc, and the split of the
@@ -291,17 +294,23 @@ class Split3Forward:
         return b
 
     def overflowed(self):
-        """True when a split of the last forward(s) since reset met |x| >= 65520 (synchronises)."""
+        """True when the last forward that ran on the model's own flag (no ``overflow=`` slot) met |x| >= 65520
+        (synchronises)."""
         return bool(self.overflow.item())
 
-    def forward(self, x, out=None):
-        """x: [N,H,W,C] f32 frames (C = 7 video / 6 image) -> alpha [N,H,W,1] f32 (``out`` if given)."""
+    def forward(self, x, out=None, overflow=None):
+        """x: [N,H,W,C] f32 frames (C = 7 video / 6 image) -> alpha [N,H,W,1] f32 (``out`` if given).  ``overflow``: the
+        one-element int32 device view this forward zeroes and sets to 1 where an activation left fp16's range
+        (default: the model's own flag, read by ``overflowed()``); no other flag is touched."""
+        if overflow is not None and not (isinstance(overflow, torch.Tensor) and overflow.dtype == torch.int32 and
+                                         overflow.numel() == 1 and overflow.device == x.device):
+            raise ValueError("overflow must be a one-element int32 view on the frames' device")
         from .unet import _levels
         n, h, w, c = x.shape
         b = self._buffers(n, h, w)
         L = _levels(h, w)
         C = self.convs
-        ovf = self.overflow
+        ovf = self.overflow if overflow is None else overflow
         ovf.zero_()
         fs = self.first_slab
         # channels 0..7 of each slab (the frame's 7 or 6 and zeros); the rest of the slabs stay zero from allocation

@@ -208,8 +208,10 @@ class UNet:
         return self.output
 
     def overflowed(self):
-        """f16x3: whether a split since the last forward began met |x| >= 65520 (its alpha is then invalid and the
-        frames belong on the bf16x6 path); synchronises.  False on the other paths."""
+        """f16x3: whether the last forward on the model's own flag met |x| >= 65520 in any split it wrote (its alpha is
+        then invalid and the frames belong on the bf16x6 path); synchronises.  False on the other paths.  build()
+        checks it and re-runs on bf16x6; a forward given its own ``overflow=`` slot reports there instead (the caller
+        reads the slot: video.VideoMatter does, per chunk, and re-runs the flagged chunks)."""
         return self.split_mode == "f16x3" and self._x6 is not None and self._x6.overflowed()
 
     def _as_input(self, input):
@@ -220,16 +222,23 @@ class UNet:
                                                                             tuple(x.shape)))
         return x
 
-    def forward(self, input, out=None):
+    def forward(self, input, out=None, overflow=None):
         """Evaluate the built network on new frames; returns .output (f32 [N,H,W,1]).  ``out`` (contiguous f32
         [N,H,W,1] on the device) receives the alpha instead of the model's own buffer (video.py writes each chunk
-        of frames straight into its slice of the result)."""
+        of frames straight into its slice of the result).  An f16x3 forward zeroes one range flag and its kernels set
+        it where an activation leaves fp16's range; forward() itself does not read it (no host synchronisation).  By
+        default that is the model's own flag (ask ``overflowed()`` afterwards; build() does, and re-runs on bf16x6);
+        ``overflow``, a one-element int32 device view (f16x3 models only), is zeroed and set instead, and the model's
+        flag is left alone."""
         x = self._as_input(input) if not (isinstance(input, torch.Tensor) and input.is_cuda and
                                           input.dtype == torch.float32) else input
         if self.convs is None:
             raise RuntimeError("call build() first")
+        if overflow is not None and self.split_mode != "f16x3":
+            raise ValueError("overflow= is the f16x3 forward's range flag; this model runs %s" %
+                             (self.split_mode or self.dtype))
         if self._x6 is not None:  # split paths (bf16x6 / f16x3): only .output and .conv1_3 (the logits) are kept
-            alpha = self._x6.forward(x, out)
+            alpha = self._x6.forward(x, out) if overflow is None else self._x6.forward(x, out, overflow)
             self._x, self._ws, self._ws_key = x, self._x6._b, self._x6._key
             self.conv1_3, self.output = self._x6.logits, alpha
             return alpha
@@ -297,13 +306,14 @@ class UNet:
         self.output = alpha
         return self.output
 
-    def capture(self, x, static=False, out=None):
+    def capture(self, x, static=False, out=None, overflow=None):
         """Record one forward over frames shaped like ``x`` into a HIP graph (torch.cuda.CUDAGraph over the same
         C-ABI launches) and return a GraphedForward: replaying it re-runs the whole forward with one host call, so
         throughput no longer depends on the host's per-launch cost.  New frames are copied into ``.input``;
         ``static=True`` records ``x`` itself as the input (no copy; x must stay allocated and in place) and ``out``
-        the alpha destination."""
-        return GraphedForward(self, x, static, out)
+        the alpha destination.  ``overflow`` (f16x3): the range-flag slot every replay zeroes and sets, as in
+        forward(); it must stay allocated with the graph."""
+        return GraphedForward(self, x, static, out, overflow)
 
     @property
     def conv1_1(self):
@@ -410,9 +420,10 @@ class GraphedForward:
     in first.  The model's weights and activation buffers are the ones captured: do not change the model's shape or
     weights afterwards (capture again instead)."""
 
-    def __init__(self, model, x, static=False, out=None):
+    def __init__(self, model, x, static=False, out=None, overflow=None):
         x = model._as_input(x)
         self.model = model
+        self.overflow = overflow  # (kept alive with the graph that writes it)
         if static:
             self.input = x
         else:
@@ -421,8 +432,8 @@ class GraphedForward:
         side = torch.cuda.Stream(device=self.input.device)
         side.wait_stream(torch.cuda.current_stream(self.input.device))
         with torch.cuda.stream(side):  # lazily built kernels/weights (folded filters, attributes) before capture
-            model.forward(self.input, out)
-        main = torch.cuda.current_stream(self.input.device)
+            model.forward(self.input, out, overflow)
+        main =torch.cuda.current_stream(self.input.device)
         main.wait_stream(side)
         torch.cuda.synchronize(self.input.device)
         # the buffer set (and any lazily allocated entry) was allocated on the side stream but the graph replays on
@@ -432,7 +443,7 @@ class GraphedForward:
             t.record_stream(main)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.output = model.forward(self.input, out)
+            self.output = model.forward(self.input, out, overflow)
         # the buffer set the graph writes stays alive with the graph; so does the forward's host-side state
         self._ws, self._ws_key = model._ws, model._ws_key
         self._skip_valid = model._skip_valid

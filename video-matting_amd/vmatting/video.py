@@ -44,7 +44,8 @@ def synthetic_frames(n, h, w, first=0, device="cuda"):
 class VideoMatter:
     """Mattes for frames[a:b] of a video batch resident on the device: ``run()`` replays the chunk graphs into
     ``alpha`` ([b-a, H, W, 1] f32).  ``frames`` is this rank's [b-a, H, W, 7] f32 block (kept alive by the
-    object: the graphs read it in place)."""
+    object: the graphs read it in place).  On an f16x3 model, chunks whose activations leave fp16's range are
+    re-run on bf16x6 and listed in ``overflowed_chunks`` (see run())."""
 
     def __init__(self, model, frames, chunk=8, graph=True, alpha=None):
         if frames.dim() != 4 or not frames.is_cuda or frames.dtype != torch.float32 or not frames.is_contiguous():
@@ -57,17 +58,41 @@ class VideoMatter:
         if tuple(self.alpha.shape) != (f, h, w, 1) or not self.alpha.is_contiguous():
             raise ValueError("alpha must be a contiguous [F,H,W,1] f32 tensor")
         self.spans = [(i, min(f, i + self.chunk)) for i in range(0, f, self.chunk)]
+        # f16x3: one range-flag slot per chunk (chunk k's forward, captured or eager, zeroes and sets slot k only), so
+        # a later chunk cannot clear an earlier one's report; the other paths have no flag and get no slot
+        self._slots = None
+        if model.split_mode == "f16x3" and self.spans:
+            self._slots = torch.zeros(len(self.spans), dtype=torch.int32, device=frames.device)
+        self._x6 = None  # the bf16x6 forward of the same parameters, built when a chunk first overflows
+        self.overflowed_chunks = []  # after run(): the chunks (indices into spans) that left fp16's range
         self.graphs = None
         if graph and f > 0:
-            self.graphs = [model.capture(frames[a:b], static=True, out=self.alpha[a:b]) for a, b in self.spans]
+            self.graphs = [model.capture(frames[a:b], static=True, out=self.alpha[a:b], overflow=self._slot(k))
+                           for k, (a, b) in enumerate(self.spans)]
+
+    def _slot(self, k):
+        return None if self._slots is None else self._slots[k:k + 1]
 
     def run(self):
+        """Matte every chunk into ``alpha``.  On an f16x3 model the chunks' range flags are then read once (one host
+        synchronisation per run) and every flagged chunk is run again, eagerly, on a bf16x6 forward of the same
+        parameters (f32 range; ~2x slower) into the same alpha slice; ``overflowed_chunks`` lists them.  The model
+        stays f16x3 and the captured graphs stay valid (its .output / .conv1_3 attributes still describe the last
+        f16x3 forward)."""
         if self.graphs is not None:
             for g in self.graphs:
                 g.replay()
         else:
-            for a, b in self.spans:
-                self.model.forward(self.frames[a:b], out=self.alpha[a:b])
+            for k, (a, b) in enumerate(self.spans):
+                self.model.forward(self.frames[a:b], out=self.alpha[a:b], overflow=self._slot(k))
+        if self._slots is not None:
+            self.overflowed_chunks = [k for k, v in enumerate(self._slots.tolist()) if v]
+            if self.overflowed_chunks and self._x6 is None:
+                from .split6 import Split6Forward
+                self._x6 = Split6Forward(self.model)  # reads the model's parameters only
+            for k in self.overflowed_chunks:
+                a, b = self.spans[k]
+                self._x6.forward(self.frames[a:b], out=self.alpha[a:b])
         return self.alpha
 
 
