@@ -31,6 +31,8 @@
 extern "C" {
 #endif
 
+/* Bumped when an existing entry point's signature, a struct layout or an enum value changes; entry points that are
+ * only added leave it alone (an older host still finds everything it binds). */
 #define VM_ABI_VERSION 1
 
 enum vm_dtype {
@@ -595,6 +597,24 @@ int vm_conv3x3_flip_weights(const float* w_hwio, int cin, int cout, float* w_fli
  * lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t). */
 int vm_adam_tf(float* var, float* m, float* v, const float* grad, long n, float lr_t, float beta1, float beta2,
                float eps, float grad_scale, void* stream);
+
+/* ---------------------------------------------------------------- inference on a decoded clip
+ * The network input from decoded uint8 frames in one pass (the reference's inference feed, loader.py:45,75-78):
+ *   cmp     uint8 [n,h,w,3] BGR composite, bg uint8 [nb,h,w,3] BGR background with nb == n, or nb == 1 for one
+ *           static plate shared by every frame, trimap uint8 [n,h,w] or NULL
+ *   out     view [n,h,w,C], C = 7 with a trimap (UNetVideo) or 6 without (UNetImage); n, h, w are read from it
+ * out channel c < 3 = f32((double)cmp - VGG_MEAN[c]), 3 + c the same of bg, VGG_MEAN = (103.939, 116.779, 123.68);
+ * channel 6 = f32((double)trimap / 255.0 - 0.5): the float64 subtraction rounded to f32 once, as the reference feeds
+ * it.  out dtype VM_F32 (any channel offset / stride) or VM_BF16: the round-to-nearest-even bf16 of those f32 values
+ * in 16-byte aligned 8-channel pixels (coff 0, cstride 8; channels C..7 are written as zero), which is the bf16 frame
+ * vm_conv3x3_pair_first*_nhwc reads.  4 pixels per thread (dword loads, 16-byte stores) when the planes are 4-byte
+ * aligned and the f32 view is dense, else one pixel per thread.  No TF counterpart (feed_dict preprocessing). */
+int vm_frames_from_u8(const uint8_t* cmp, const uint8_t* bg, const uint8_t* trimap, int nb, vm_tensor* out,
+                      void* stream);
+
+/* alpha f32 [pixels] -> 8- or 16-bit matte: q = (T)min(max(rintf(alpha * M), 0), M), M = 255.f (bits 8, uint8 out) or
+ * 65535.f (bits 16, uint16 out); f32 product, ties to even, NaN -> 0. */
+int vm_matte_quantize(const float* alpha, long pixels, int bits, void* out, void* stream);
 
 #ifdef __cplusplus
 }

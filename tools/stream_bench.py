@@ -1,0 +1,214 @@
+"""Measure the clip ends: the ingest and quantise kernels, the torch route they replace, the host link, and the
+streamed pipeline beside the resident-frames VideoMatter.  Prints one JSON line and writes it to
+profiles/ingest_stream.json.
+
+    python tools/stream_bench.py [--frames 64] [--chunk 8] [--height 1080] [--width 1920] [--reps 9]
+
+Kernel times are hipEvent medians over ``--reps`` runs after a warm-up; every run of a kernel works on another of
+several buffer sets, so the 83 MB alpha of the quantise kernel does not sit in the 256 MB memory-side cache between
+runs.  GB/s are algorithmic bytes (read once + written once) over that time; ``hbm_frac`` is that over the 8 TB/s peak.
+Each step runs under its own wall-clock limit (``--step-limit`` seconds): a step that overruns ends the tool with an
+error instead of starting the next one.
+"""
+
+import argparse
+import json
+import os
+import signal
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(REPO, "video-matting_amd"), REPO):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+HBM_PEAK = 8.0e12  # MI355X HBM3E, bytes/s
+VGG_MEAN = (103.939, 116.779, 123.68)
+
+
+class StepTimeout(Exception):
+    pass
+
+
+def step(name, limit, fn):
+    """Run one measurement under its own wall-clock limit."""
+    def on_alarm(signum, frame):
+        raise StepTimeout("step %r exceeded %d s" % (name, limit))
+    signal.signal(signal.SIGALRM, on_alarm)
+    signal.alarm(limit)
+    t0 = time.time()
+    try:
+        return fn()
+    finally:
+        signal.alarm(0)
+        print("# %-22s %.1f s" % (name, time.time() - t0), file=sys.stderr)
+
+
+def event_ms(fns, reps, warmup=3):
+    """Median hipEvent time of one call: every timed window runs each of ``fns`` once (the same work on different
+    buffers, back to back) and is divided by their number."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for fn in fns:
+            fn()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1) / len(fns))
+    return statistics.median(times)
+
+
+def rate(nbytes, ms):
+    return {"ms": round(ms, 4), "GBps": round(nbytes / ms / 1e6, 1), "hbm_frac": round(nbytes / (ms * 1e-3) / HBM_PEAK, 3)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--chunk", type=int, default=8)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--sets", type=int, default=3, help="buffer sets the kernel timings cycle through")
+    ap.add_argument("--step-limit", type=int, default=150)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ingest_stream.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("stream_bench needs a ROCm GPU")
+    from vmatting import FrameStream, ops, unet, video
+    from vmatting.weights import synthetic_vgg16
+    n, h, w, F = a.chunk, a.height, a.width, a.frames
+    px = n * h * w
+    res = {"shape": [n, h, w], "frames": F, "reps": a.reps, "device": torch.cuda.get_device_name(0),
+           "hbm_peak_GBps": HBM_PEAK / 1e9}
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0)
+    sets = []
+    for _ in range(a.sets):
+        sets.append(dict(cmp=torch.randint(0, 256, (n, h, w, 3), generator=g, device="cuda", dtype=torch.uint8),
+                         bg=torch.randint(0, 256, (n, h, w, 3), generator=g, device="cuda", dtype=torch.uint8),
+                         tri=torch.randint(0, 256, (n, h, w), generator=g, device="cuda", dtype=torch.uint8),
+                         alpha=torch.rand((n, h, w, 1), generator=g, device="cuda")))
+
+    # ---- the kernels
+    def kernels():
+        out = {}
+        f32 = [torch.empty((n, h, w, 7), dtype=torch.float32, device="cuda") for _ in sets]
+        ms = event_ms([lambda s=s, o=o: ops.frames_from_u8(s["cmp"], s["bg"], s["tri"], out=o)
+                       for s, o in zip(sets, f32)], a.reps)
+        out["frames_from_u8_f32_c7"] = rate(px * (7 + 28), ms)
+        ms = event_ms([lambda s=s, o=o: ops.frames_from_u8(s["cmp"], s["bg"][0], s["tri"], out=o)
+                       for s, o in zip(sets, f32)], a.reps)
+        out["frames_from_u8_f32_c7_static_bg"] = rate(px * (4 + 28) + h * w * 3, ms)
+        # the parent commit's only route to the same f32 frames: torch ops on the device
+        mean = torch.tensor(VGG_MEAN, dtype=torch.float64, device="cuda")
+
+        def torch_route(s):
+            return torch.cat([(s["cmp"].double() - mean).float(), (s["bg"].double() - mean).float(),
+                              (s["tri"].double() / 255.0 - 0.5).float()[..., None]], -1)
+        # the same values, so the same work is compared
+        assert torch.equal(torch_route(sets[0]), ops.frames_from_u8(sets[0]["cmp"], sets[0]["bg"], sets[0]["tri"]))
+        ms_t = event_ms([lambda s=s: torch_route(s) for s in sets], a.reps)
+        out["torch_route_f32_c7"] = {"ms": round(ms_t, 4)}
+        out["ingest_speedup_over_torch"] = round(ms_t / out["frames_from_u8_f32_c7"]["ms"], 2)
+        del f32
+        b16 = [torch.empty((n, h, w, 8), dtype=torch.bfloat16, device="cuda")[..., :7] for _ in sets]
+        ms = event_ms([lambda s=s, o=o: ops.frames_from_u8(s["cmp"], s["bg"], s["tri"], out=o)
+                       for s, o in zip(sets, b16)], a.reps)
+        out["frames_from_u8_bf16x8"] = rate(px * (7 + 16), ms)
+        del b16
+        for bits in (8, 16):
+            q = [torch.empty((n, h, w), dtype=torch.uint8 if bits == 8 else torch.uint16, device="cuda") for _ in sets]
+            ms = event_ms([lambda s=s, o=o: ops.matte_quantize(s["alpha"], out=o, bits=bits)
+                           for s, o in zip(sets, q)], a.reps)
+            out["matte_quantize_u%d" % bits] = rate(px * (4 + bits // 8), ms)
+        return out
+    res.update(step("kernels", a.step_limit, kernels))
+
+    # ---- the host link: one uint8 chunk (cmp + bg + trimap = 7 B per pixel) from pinned memory, one matte back
+    def link():
+        hc = [torch.empty(s, dtype=torch.uint8).pin_memory() for s in ((n, h, w, 3), (n, h, w, 3), (n, h, w))]
+        dc = [sets[0]["cmp"], sets[0]["bg"], sets[0]["tri"]]
+        ms_up = event_ms([lambda: [d.copy_(s, non_blocking=True) for d, s in zip(dc, hc)]], a.reps)
+        hq, dq = torch.empty((n, h, w), dtype=torch.uint8).pin_memory(), torch.empty((n, h, w), dtype=torch.uint8,
+                                                                                     device="cuda")
+        ms_dn = event_ms([lambda: hq.copy_(dq, non_blocking=True)], a.reps)
+        src = [np.frombuffer(np.random.RandomState(2).bytes(t.numel()), np.uint8).reshape(tuple(t.shape)) for t in hc]
+        t0 = time.perf_counter()
+        for _ in range(3):
+            for s, t in zip(src, hc):
+                t.numpy()[...] = s
+        ms_host = (time.perf_counter() - t0) / 3 * 1e3
+        return {"h2d_pinned_u8_chunk": {"ms": round(ms_up, 3), "GBps": round(px * 7 / ms_up / 1e6, 1)},
+                "d2h_pinned_u8_matte": {"ms": round(ms_dn, 3), "GBps": round(px / ms_dn / 1e6, 1)},
+                "host_copy_into_pinned": {"ms": round(ms_host, 3), "GBps": round(px * 7 / ms_host / 1e6, 1)}}
+    res.update(step("link", a.step_limit, link))
+    del sets
+    torch.cuda.empty_cache()
+
+    # ---- the pipeline: FrameStream (bf16, u8 mattes, depth 2) beside VideoMatter.run() on resident f32 frames
+    np.random.seed(0)
+    model = unet.UNetVideo(synthetic_vgg16(0), dtype="bf16", device="cuda").prepare()
+
+    def resident():
+        frames = video.synthetic_frames(F, h, w)
+        vm = video.VideoMatter(model, frames, chunk=n)
+        ms = event_ms([vm.run], max(3, a.reps // 2), warmup=2)
+        return {"video_matter_resident_f32": {"ms": round(ms, 2), "frames_per_s": round(F / ms * 1e3, 1)}}
+    res.update(step("resident", a.step_limit, resident))
+    torch.cuda.empty_cache()
+
+    def streamed():
+        rs = np.random.RandomState(1)
+        k = min(F, 2 * n)  # two distinct chunks of host frames, cycled (the source hands out views of them)
+        cmp, bg = (rs.randint(0, 256, (k, h, w, 3), dtype=np.uint8) for _ in range(2))
+        tri = rs.choice(np.array([0, 128, 255], np.uint8), (k, h, w))
+
+        def source():
+            for i in range(0, F, n):
+                m = min(n, F - i)
+                o = i % k
+                yield cmp[o:o + m], bg[o:o + m], tri[o:o + m]
+        fs = FrameStream(model, h, w, chunk=n, depth=2, out="u8")
+
+        def run():
+            t0 = time.perf_counter()
+            tot = sum(m.shape[0] for m in fs.run(source()))
+            torch.cuda.synchronize()
+            assert tot == F
+            return (time.perf_counter() - t0) * 1e3
+        run()
+        ms = statistics.median(run() for _ in range(max(3, a.reps // 2)))
+        return {"frame_stream_bf16_u8_depth2": {"ms": round(ms, 2), "frames_per_s": round(F / ms * 1e3, 1)}}
+    res.update(step("streamed", a.step_limit, streamed))
+
+    # ---- which leg bounds the stream: per chunk, upload vs compute vs download (device legs overlap across slots),
+    # and the host's own serial work per chunk (the copy into pinned memory + the copy of the matte out of it)
+    per_chunk = res["video_matter_resident_f32"]["ms"] * n / F
+    legs = {"upload": res["h2d_pinned_u8_chunk"]["ms"],
+            "compute": round(per_chunk + res["frames_from_u8_bf16x8"]["ms"] + res["matte_quantize_u8"]["ms"], 3),
+            "download": res["d2h_pinned_u8_matte"]["ms"],
+            "host_copy": res["host_copy_into_pinned"]["ms"]}
+    res["legs_ms_per_chunk"] = legs
+    res["bounding_leg"] = max(legs, key=legs.get)
+    res["stream_keeps_of_resident"] = round(res["frame_stream_bf16_u8_depth2"]["frames_per_s"] /
+                                            res["video_matter_resident_f32"]["frames_per_s"], 3)
+    line = json.dumps(res)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,211 @@
+// The two ends of inference on a decoded clip: uint8 frames -> the network's input (vm_frames_from_u8) and f32
+// alpha -> 8- / 16-bit mattes (vm_matte_quantize).  Both are pure memory traffic (7 B in, 28 or 16 B out per pixel;
+// 4 B in, 1 or 2 B out), so each thread takes 4 pixels: dword loads of the u8 planes, 16-byte stores of the frame,
+// 16-byte loads of the alpha, one packed store of the matte; a scalar tail covers pixels % 4.
+//
+// Arithmetic of vm_frames_from_u8 (the reference's inference feed, loader.py:45,75-78): the mean and the 0.5 are
+// subtracted in float64 and the result is rounded to f32 once; the bf16 form is the RNE bf16 of that f32, the rounding
+// Chunk<T>::pack applies when the pair kernel reads an f32 frame.  The BGR planes are computed directly in double
+// (convert, subtract, convert); the trimap's u / 255.0 - 0.5 comes from a 256-entry table each block builds in double
+// (one f64 division per entry instead of one per pixel).
+#include "vm_common.h"
+
+namespace vm {
+namespace {
+
+__device__ __forceinline__ double vgg_mean_d(int c) { return c == 0 ? 103.939 : c == 1 ? 116.779 : 123.68; }
+
+__device__ __forceinline__ float bgr_value(uint32_t u, int c) { return (float)((double)u - vgg_mean_d(c)); }
+
+struct IngestArgs {
+  const uint8_t* cmp;
+  const uint8_t* bg;
+  const uint8_t* tri;  // null: 6 channels
+  void* out;           // first element of the view (coff applied)
+  long total;          // n * h * w
+  long hw;             // pixels per frame (bg broadcast: nb == 1)
+  int bg_bcast;        // 1: bg is one [h,w,3] plate
+  int cstride;         // elements per output pixel
+  int vec;             // 1: the u8 planes are 4-byte aligned (dword loads of 4-pixel groups)
+};
+
+// one pixel's C values (C = 7 with a trimap, 6 without) + zeros up to 8
+template <int C>
+__device__ __forceinline__ void pixel_values(const IngestArgs& a, const float* lut, long pix, float* v) {
+  const long bp = a.bg_bcast ? pix % a.hw : pix;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    v[c] = bgr_value(a.cmp[pix * 3 + c], c);
+    v[3 + c] = bgr_value(a.bg[bp * 3 + c], c);
+  }
+  v[6] = C == 7 ? lut[a.tri[pix]] : 0.f;
+  v[7] = 0.f;
+}
+
+// BF8 = 0: f32 pixels of C channels at any stride; BF8 = 1: bf16 pixels of 8 channels (C values + zeros), 16 bytes
+template <int C, int BF8>
+__device__ __forceinline__ void store_pixel(const IngestArgs& a, long pix, const float* v) {
+  if constexpr (BF8) {
+    reinterpret_cast<uint4*>(a.out)[pix] = Chunk<uint16_t>::pack(v);
+  } else {
+    float* o = reinterpret_cast<float*>(a.out) + pix * a.cstride;
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = v[c];
+  }
+}
+
+// 12 bytes = 4 BGR pixels starting at byte offset `off` (a multiple of 12 from a 4-byte aligned plane)
+__device__ __forceinline__ void load12(const uint8_t* p, long off, uint32_t* w) {
+  const uint32_t* q = reinterpret_cast<const uint32_t*>(p + off);
+  w[0] = q[0]; w[1] = q[1]; w[2] = q[2];
+}
+__device__ __forceinline__ uint32_t byte_of(const uint32_t* w, int i) { return (w[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
+
+// DENSE = 1: f32 [pixels, C] without gaps, 16-byte aligned -> 4 pixels are C float4 stores; BF8 = 1: 4 uint4 stores.
+// DENSE = 0 and BF8 = 0: f32 at a channel offset / stride, one pixel per thread and scalar stores.
+template <int C, int BF8, int DENSE>
+__global__ void __launch_bounds__(256) frames_from_u8_kernel(const IngestArgs a) {
+  __shared__ float lut[256];
+  if (C == 7) {
+    lut[threadIdx.x] = (float)((double)threadIdx.x / 255.0 - 0.5);
+    __syncthreads();
+  }
+  const long tid = (long)blockIdx.x * 256 + threadIdx.x, nthreads = (long)gridDim.x * 256;
+  const bool vec = a.vec && (BF8 || DENSE);
+  const long groups = vec ? a.total / 4 : 0;
+  const bool bg_vec = !a.bg_bcast || a.hw % 4 == 0;  // a 4-pixel group never straddles the plate's end
+  for (long g = tid; g < groups; g += nthreads) {
+    const long p0 = g * 4;
+    uint32_t wc[3], wb[3], wt = 0;
+    load12(a.cmp, p0 * 3, wc);
+    if (bg_vec) {
+      load12(a.bg, (a.bg_bcast ? p0 % a.hw : p0) * 3, wb);
+    } else {
+      wb[0] = wb[1] = wb[2] = 0;
+#pragma unroll
+      for (int i = 0; i < 12; ++i) wb[i >> 2] |= (uint32_t)a.bg[((p0 + i / 3) % a.hw) * 3 + i % 3] << ((i & 3) * 8);
+    }
+    if (C == 7) wt = *reinterpret_cast<const uint32_t*>(a.tri + p0);
+    float v[4][8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        v[j][c] = bgr_value(byte_of(wc, 3 * j + c), c);
+        v[j][3 + c] = bgr_value(byte_of(wb, 3 * j + c), c);
+      }
+      v[j][6] = C == 7 ? lut[(wt >> (8 * j)) & 0xffu] : 0.f;
+      v[j][7] = 0.f;
+    }
+    if constexpr (BF8) {
+      uint4* o = reinterpret_cast<uint4*>(a.out) + p0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = Chunk<uint16_t>::pack(v[j]);
+    } else {
+      float f[4 * C];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int c = 0; c < C; ++c) f[j * C + c] = v[j][c];
+      float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + p0 * C);
+#pragma unroll
+      for (int q = 0; q < C; ++q) o[q] = make_float4(f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]);
+    }
+  }
+  // scalar tail (total % 4 pixels), or every pixel when the planes are unaligned / the output is strided
+  for (long pix = groups * 4 + tid; pix < a.total; pix += nthreads) {
+    float v[8];
+    pixel_values<C>(a, lut, pix, v);
+    store_pixel<C, BF8>(a, pix, v);
+  }
+}
+
+template <int BITS>
+__device__ __forceinline__ uint32_t quantize1(float x) {
+  constexpr float M = BITS == 8 ? 255.f : 65535.f;
+  float r = rintf(x * M);    // f32 product, round half to even
+  r = r >= 0.f ? r : 0.f;    // NaN and negatives -> 0
+  r = r > M ? M : r;
+  return (uint32_t)r;
+}
+
+// 4 alphas per thread: one 16-byte load, one 4-byte (u8) or 8-byte (u16) store; groups = 0 when unaligned
+template <int BITS>
+__global__ void __launch_bounds__(256) matte_quantize_kernel(const float* __restrict__ alpha, long pixels, long groups,
+                                                             void* __restrict__ out) {
+  const long tid = (long)blockIdx.x * 256 + threadIdx.x, nthreads = (long)gridDim.x * 256;
+  for (long g = tid; g < groups; g += nthreads) {
+    const float4 a = reinterpret_cast<const float4*>(alpha)[g];
+    const uint32_t q0 = quantize1<BITS>(a.x), q1 = quantize1<BITS>(a.y), q2 = quantize1<BITS>(a.z),
+                   q3 = quantize1<BITS>(a.w);
+    if constexpr (BITS == 8)
+      reinterpret_cast<uint32_t*>(out)[g] = q0 | (q1 << 8) | (q2 << 16) | (q3 << 24);
+    else
+      reinterpret_cast<uint2*>(out)[g] = make_uint2(q0 | (q1 << 16), q2 | (q3 << 16));
+  }
+  for (long i = groups * 4 + tid; i < pixels; i += nthreads) {
+    const uint32_t q = quantize1<BITS>(alpha[i]);
+    if constexpr (BITS == 8)
+      reinterpret_cast<uint8_t*>(out)[i] = (uint8_t)q;
+    else
+      reinterpret_cast<uint16_t*>(out)[i] = (uint16_t)q;
+  }
+}
+
+}  // namespace
+}  // namespace vm
+
+using namespace vm;
+
+extern "C" int vm_frames_from_u8(const uint8_t* cmp, const uint8_t* bg, const uint8_t* trimap, int nb,
+                                 vm_tensor* out, void* stream) {
+  if (!cmp || !bg || !out || !out->ptr) return fail(VM_EINVAL, "frames_from_u8: null cmp / bg / output");
+  if (out->n <= 0 || out->h <= 0 || out->w <= 0 || out->coff < 0 || out->c <= 0 || out->coff + out->c > out->cstride)
+    return fail(VM_EINVAL, "frames_from_u8: bad output view [%d,%d,%d,%d] at %d of %d", out->n, out->h, out->w, out->c,
+                out->coff, out->cstride);
+  if (nb != 1 && nb != out->n) return fail(VM_EINVAL, "frames_from_u8: %d backgrounds for %d frames (1 or n)", nb, out->n);
+  if (out->c != (trimap ? 7 : 6))
+    return fail(VM_EINVAL, "frames_from_u8: %d output channels %s a trimap (7 with, 6 without)", out->c,
+                trimap ? "with" : "without");
+  if (out->dtype != VM_F32 && out->dtype != VM_BF16)
+    return fail(VM_EINVAL, "frames_from_u8: output dtype %d (f32 or bf16)", out->dtype);
+  const bool bf = out->dtype == VM_BF16;
+  if (bf && (out->coff != 0 || out->cstride != 8 || reinterpret_cast<uintptr_t>(out->ptr) % 16))
+    return fail(VM_EUNSUPPORTED, "frames_from_u8: a bf16 frame is 16-byte aligned 8-channel pixels (channel offset 0)");
+  IngestArgs a{};
+  a.cmp = cmp; a.bg = bg; a.tri = trimap;
+  a.out = reinterpret_cast<char*>(out->ptr) + (size_t)out->coff * (bf ? 2 : 4);
+  a.hw = (long)out->h * out->w;
+  a.total = a.hw * out->n;
+  a.bg_bcast = nb == 1 && out->n > 1;
+  a.cstride = out->cstride;
+  a.vec = reinterpret_cast<uintptr_t>(cmp) % 4 == 0 && reinterpret_cast<uintptr_t>(bg) % 4 == 0 &&
+          reinterpret_cast<uintptr_t>(trimap) % 4 == 0;
+  const bool dense = !bf && out->cstride == out->c && reinterpret_cast<uintptr_t>(a.out) % 16 == 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool grouped = a.vec && (bf || dense);
+  const dim3 grid(grid_for(grouped ? (a.total + 3) / 4 : a.total, 256, 256 * 32));
+#define VM_INGEST(C, BF8, DENSE) \
+  hipLaunchKernelGGL((frames_from_u8_kernel<C, BF8, DENSE>), grid, dim3(256), 0, st, a)
+  if (trimap) {
+    if (bf) VM_INGEST(7, 1, 0); else if (dense) VM_INGEST(7, 0, 1); else VM_INGEST(7, 0, 0);
+  } else {
+    if (bf) VM_INGEST(6, 1, 0); else if (dense) VM_INGEST(6, 0, 1); else VM_INGEST(6, 0, 0);
+  }
+#undef VM_INGEST
+  return check_launch("frames_from_u8");
+}
+
+extern "C" int vm_matte_quantize(const float* alpha, long pixels, int bits, void* out, void* stream) {
+  if (!alpha || !out || pixels <= 0) return fail(VM_EINVAL, "matte_quantize: null pointer or no pixels");
+  if (bits != 8 && bits != 16) return fail(VM_EINVAL, "matte_quantize: %d-bit mattes (8 or 16)", bits);
+  const bool vec = reinterpret_cast<uintptr_t>(alpha) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % (bits / 2) == 0;
+  const long groups = vec ? pixels / 4 : 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid(grid_for(vec ? (pixels + 3) / 4 : pixels, 256, 256 * 32));
+  if (bits == 8)
+    hipLaunchKernelGGL((matte_quantize_kernel<8>), grid, dim3(256), 0, st, alpha, pixels, groups, out);
+  else
+    hipLaunchKernelGGL((matte_quantize_kernel<16>), grid, dim3(256), 0, st, alpha, pixels, groups, out);
+  return check_launch("matte_quantize");
+}

@@ -186,6 +186,8 @@ SIGNATURES = [
     ("vm_conv3x3_flip_weights", c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     ("vm_adam_tf", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float,
                            c_float, c_void_p]),
+    ("vm_frames_from_u8", c_int, [c_void_p, c_void_p, c_void_p, c_int, P, c_void_p]),
+    ("vm_matte_quantize", c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p]),
 ]
 
 _lib = None

@@ -888,6 +888,71 @@ def trimap_from_matte(matte, dilate=1, crop=3, out=None):
     return out
 
 
+# ---------------------------------------------------------------- inference on a decoded clip
+
+def _check_u8_frames(cmp, bg, trimap):
+    """Shapes / dtypes of decoded frames (torch tensors or numpy arrays): cmp u8 [n,h,w,3], bg u8 [n,h,w,3] | [1,h,w,3] |
+    [h,w,3], trimap u8 [n,h,w] | None -> (n, h, w, nb)."""
+    for name, t in (("cmp", cmp), ("bg", bg), ("trimap", trimap)):
+        if t is not None and str(t.dtype).split(".")[-1] != "uint8":
+            raise TypeError("%s must be uint8, got %s" % (name, t.dtype))
+    if len(cmp.shape) != 4 or cmp.shape[3] != 3 or cmp.shape[0] < 1:
+        raise ValueError("cmp must be [n,h,w,3] BGR, got %s" % (tuple(cmp.shape),))
+    n, h, w, _ = (int(v) for v in cmp.shape)
+    if tuple(bg.shape) not in ((n, h, w, 3), (1, h, w, 3), (h, w, 3)):
+        raise ValueError("bg must be [n,h,w,3], or one [h,w,3] plate, for cmp %s; got %s" %
+                         (tuple(cmp.shape), tuple(bg.shape)))
+    if trimap is not None and tuple(trimap.shape) != (n, h, w):
+        raise ValueError("trimap must be [n,h,w] = %s, got %s" % ((n, h, w), tuple(trimap.shape)))
+    return n, h, w, (n if tuple(bg.shape) == (n, h, w, 3) else 1)
+
+
+def frames_from_u8(cmp, bg, trimap=None, out=None, dtype=torch.float32):
+    """vm_frames_from_u8: decoded uint8 frames -> the network input in one pass.  cmp u8 [n,h,w,3] BGR, bg u8
+    [n,h,w,3] or one static plate [h,w,3] / [1,h,w,3], trimap u8 [n,h,w] or None -> ``out`` [n,h,w,C] (C = 7 with a
+    trimap, 6 without): channels = f32((double)u - VGG_MEAN) and f32((double)u / 255 - .5) as the reference feeds them.
+    ``out``: an f32 NHWC view (dense or a channel slice), or the [..., :C] view of a bf16 [n,h,w,8] buffer (whose
+    channels C..7 are zeroed); allocated in ``dtype`` when None."""
+    n, h, w, nb = _check_u8_frames(cmp, bg, trimap)
+    for t in (cmp, bg) + (() if trimap is None else (trimap,)):
+        _require_gpu(t)
+        if not t.is_contiguous():
+            raise ValueError("frames_from_u8: contiguous uint8 tensors expected")
+    c = 6 if trimap is None else 7
+    if out is None:
+        if dtype == torch.bfloat16:
+            out = torch.empty((n, h, w, 8), dtype=torch.bfloat16, device=cmp.device)[..., :c]
+        elif dtype == torch.float32:
+            out = torch.empty((n, h, w, c), dtype=torch.float32, device=cmp.device)
+        else:
+            raise TypeError("frames_from_u8: f32 or bf16 output, got %s" % dtype)
+    if tuple(out.shape) != (n, h, w, c):
+        raise ValueError("frames_from_u8: out must be [n,h,w,%d] = %s, got %s" % (c, (n, h, w, c), tuple(out.shape)))
+    ov = nhwc(out)
+    check(lib().vm_frames_from_u8(_ptr(cmp), _ptr(bg), _ptr(trimap), nb, ctypes.byref(ov), stream_handle()),
+          "frames_from_u8")
+    return out
+
+
+def matte_quantize(alpha, out=None, bits=8):
+    """vm_matte_quantize: f32 alpha (any shape, contiguous) -> uint8 (bits 8) or uint16 (bits 16) of the same shape:
+    min(max(rint(alpha * M), 0), M), M = 255 / 65535, ties to even, NaN -> 0."""
+    _require_gpu(alpha)
+    if bits not in (8, 16):
+        raise ValueError("matte_quantize: bits 8 or 16, got %r" % (bits,))
+    qt = torch.uint8 if bits == 8 else torch.uint16
+    if alpha.dtype != torch.float32 or not alpha.is_contiguous():
+        raise ValueError("matte_quantize: contiguous f32 alpha expected")
+    if out is None:
+        out = torch.empty(alpha.shape, dtype=qt, device=alpha.device)
+    _require_gpu(out)
+    if out.dtype != qt or out.numel() != alpha.numel() or not out.is_contiguous():
+        raise ValueError("matte_quantize: out must be a contiguous %s tensor of %d elements" % (qt, alpha.numel()))
+    if alpha.numel():
+        check(lib().vm_matte_quantize(_ptr(alpha), alpha.numel(), bits, _ptr(out), stream_handle()), "matte_quantize")
+    return out
+
+
 # ---------------------------------------------------------------- training step (train.py:288-343, config 5)
 
 def matting_loss_backward(pred, gt, raw_fg, in_bg, in_cmp, out=None):

@@ -214,7 +214,17 @@ class UNet:
         reads the slot: video.VideoMatter does, per chunk, and re-runs the flagged chunks)."""
         return self.split_mode == "f16x3" and self._x6 is not None and self._x6.overflowed()
 
+    def _native_input(self, x):
+        """Whether ``x`` is a frame already in the plain bf16 path's compute dtype: the [..., :IN_CH] view of a bf16
+        [N,H,W,8] device buffer whose pad channels are zero (ops.frames_from_u8 writes it), which the first pair
+        kernel reads as it is.  The fp32 and split paths take f32 frames only."""
+        return (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.bfloat16 and not self.x6mode and
+                self.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[-1] == self.IN_CH and
+                x.stride(3) == 1 and x.stride(2) == 8 and x.data_ptr() % 16 == 0)
+
     def _as_input(self, input):
+        if self._native_input(input):
+            return input
         x = input if isinstance(input, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(input, np.float32))
         x = x.to(self.device, torch.float32)
         if x.dim() != 4 or x.shape[-1] != self.IN_CH:
@@ -229,7 +239,8 @@ class UNet:
         it where an activation leaves fp16's range; forward() itself does not read it (no host synchronisation).  By
         default that is the model's own flag (ask ``overflowed()`` afterwards; build() does, and re-runs on bf16x6);
         ``overflow``, a one-element int32 device view (f16x3 models only), is zeroed and set instead, and the model's
-        flag is left alone."""
+        flag is left alone.  A plain bf16 model also takes the frame in its compute dtype (see _native_input): the
+        bf16 rounding of the same f32 values, so the result is the f32 frame's bit for bit."""
         x = self._as_input(input) if not (isinstance(input, torch.Tensor) and input.is_cuda and
                                           input.dtype == torch.float32) else input
         if self.convs is None:
@@ -262,9 +273,13 @@ class UNet:
             self._c11 = None
             self._in8_valid = False
         else:
-            ops.convert(x, b["in8"])
-            xin = b["in8"][..., :c]
-            self._in8_valid = True
+            if x.dtype == torch.bfloat16:  # a frame in the compute dtype IS in8 (8-channel pixels, zero pad)
+                xin = x
+                self._in8_valid = False
+            else:
+                ops.convert(x, b["in8"])
+                xin = b["in8"][..., :c]
+                self._in8_valid = True
             self._c11 = ops.conv3x3(xin, C["conv1_1"], "relu", out=b["c11"])
             ops.conv3x3(b["c11"], C["conv1_2"], "relu", out=b["cat1"][..., 64:], pool_out=b["p1"])
         self._x = x
@@ -306,23 +321,28 @@ class UNet:
         self.output = alpha
         return self.output
 
-    def capture(self, x, static=False, out=None, overflow=None):
+    def capture(self, x, static=False, out=None, overflow=None, pre=None, post=None):
         """Record one forward over frames shaped like ``x`` into a HIP graph (torch.cuda.CUDAGraph over the same
         C-ABI launches) and return a GraphedForward: replaying it re-runs the whole forward with one host call, so
         throughput no longer depends on the host's per-launch cost.  New frames are copied into ``.input``;
         ``static=True`` records ``x`` itself as the input (no copy; x must stay allocated and in place) and ``out``
         the alpha destination.  ``overflow`` (f16x3): the range-flag slot every replay zeroes and sets, as in
-        forward(); it must stay allocated with the graph."""
-        return GraphedForward(self, x, static, out, overflow)
+        forward(); it must stay allocated with the graph.  ``pre`` / ``post``: callables recorded into the same graph
+        before / after the forward, on the same stream (the streamed pipeline's ingest before it, its quantisation and
+        download after it); they take no arguments and must only launch work on the current stream."""
+        return GraphedForward(self, x, static, out, overflow, pre, post)
 
     @property
     def conv1_1(self):
         """unet.py:170 conv1_1 — with fuse_first the forward never writes it to HBM, so it is evaluated here."""
         if self._c11 is None and self._ws is not None:
-            if not self._in8_valid:
-                ops.convert(self._x, self._ws["in8"])
-                self._in8_valid = True
-            xin = self._ws["in8"][..., :self.IN_CH]
+            if self._x.dtype == torch.bfloat16:
+                xin = self._x
+            else:
+                if not self._in8_valid:
+                    ops.convert(self._x, self._ws["in8"])
+                    self._in8_valid = True
+                xin = self._ws["in8"][..., :self.IN_CH]
             self._c11 = ops.conv3x3(xin, self.convs["conv1_1"], "relu", out=self._ws["c11"])
         return self._c11
 
@@ -420,19 +440,30 @@ class GraphedForward:
     in first.  The model's weights and activation buffers are the ones captured: do not change the model's shape or
     weights afterwards (capture again instead)."""
 
-    def __init__(self, model, x, static=False, out=None, overflow=None):
+    def __init__(self, model, x, static=False, out=None, overflow=None, pre=None, post=None):
         x = model._as_input(x)
         self.model = model
         self.overflow = overflow  # (kept alive with the graph that writes it)
         if static:
             self.input = x
+        elif x.dtype == torch.bfloat16:  # a frame in the compute dtype: its own 8-channel buffer, pad zero
+            self.input = torch.zeros(tuple(x.shape[:3]) + (8,), dtype=x.dtype, device=x.device)[..., :x.shape[3]]
+            self.input.copy_(x)
         else:
             self.input = torch.empty_like(x)
             self.input.copy_(x)
+
+        def run():
+            if pre is not None:
+                pre()
+            o = model.forward(self.input, out, overflow)
+            if post is not None:
+                post()
+            return o
         side = torch.cuda.Stream(device=self.input.device)
         side.wait_stream(torch.cuda.current_stream(self.input.device))
         with torch.cuda.stream(side):  # lazily built kernels/weights (folded filters, attributes) before capture
-            model.forward(self.input, out, overflow)
+            run()
         main =torch.cuda.current_stream(self.input.device)
         main.wait_stream(side)
         torch.cuda.synchronize(self.input.device)
@@ -443,7 +474,7 @@ class GraphedForward:
             t.record_stream(main)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.output = model.forward(self.input, out, overflow)
+            self.output = run()
         # the buffer set the graph writes stays alive with the graph; so does the forward's host-side state
         self._ws, self._ws_key = model._ws, model._ws_key
         self._skip_valid = model._skip_valid

@@ -13,7 +13,7 @@ activation buffers (they run in order on one stream).
 
 import torch
 
-from . import parallel
+from . import ops, parallel
 
 VGG_MEAN = (103.939, 116.779, 123.68)  # params.py:10
 
@@ -47,11 +47,14 @@ class VideoMatter:
     object: the graphs read it in place).  On an f16x3 model, chunks whose activations leave fp16's range are
     re-run on bf16x6 and listed in ``overflowed_chunks`` (see run())."""
 
-    def __init__(self, model, frames, chunk=8, graph=True, alpha=None):
-        if frames.dim() != 4 or not frames.is_cuda or frames.dtype != torch.float32 or not frames.is_contiguous():
+    def __init__(self, model, frames, chunk=8, graph=True, alpha=None, _u8=None):
+        # _u8 (from_uint8 only): the (cmp, bg, trimap) uint8 tensors each chunk's frames are made from, in its graph
+        if _u8 is None and (frames.dim() != 4 or not frames.is_cuda or frames.dtype != torch.float32 or
+                            not frames.is_contiguous()):
             raise ValueError("frames must be a contiguous [F,H,W,C] f32 device tensor")
         model.prepare()
         self.model, self.frames, self.chunk = model, frames, max(1, int(chunk))
+        self._u8 = _u8
         f, h, w, _ = frames.shape
         self.alpha = alpha if alpha is not None else torch.empty((f, h, w, 1), dtype=torch.float32,
                                                                  device=frames.device)
@@ -67,8 +70,38 @@ class VideoMatter:
         self.overflowed_chunks = []  # after run(): the chunks (indices into spans) that left fp16's range
         self.graphs = None
         if graph and f > 0:
-            self.graphs = [model.capture(frames[a:b], static=True, out=self.alpha[a:b], overflow=self._slot(k))
+            self.graphs = [model.capture(frames[a:b], static=True, out=self.alpha[a:b], overflow=self._slot(k),
+                                         pre=None if _u8 is None else (lambda k=k: self._ingest(k)))
                            for k, (a, b) in enumerate(self.spans)]
+
+    @classmethod
+    def from_uint8(cls, model, cmp, bg, trimap=None, chunk=8, graph=True, alpha=None):
+        """A VideoMatter over decoded frames resident on the device: cmp uint8 [F,H,W,3] BGR, bg uint8 [F,H,W,3] or
+        one static plate [H,W,3], trimap uint8 [F,H,W] (UNetVideo) or None (UNetImage).  The frame buffer is
+        allocated in the model's input format (bf16 8-channel pixels for a plain bf16 model, f32 otherwise) and
+        every chunk's frames are made by ops.frames_from_u8 inside that chunk's graph (or eagerly), so ``run()``
+        reads the uint8 tensors as they are then: the float64 mean subtraction of the reference's feed
+        (loader.py:45,75-78), bit for bit.  Otherwise it is the VideoMatter of those frames."""
+        f, h, w, _ = ops._check_u8_frames(cmp, bg, trimap)
+        c = 6 if trimap is None else 7
+        if c != model.IN_CH:
+            raise ValueError("%s takes %d input channels: trimap %s" % (type(model).__name__, model.IN_CH,
+                                                                       "required" if model.IN_CH == 7 else "not taken"))
+        for t in (cmp, bg) + (() if trimap is None else (trimap,)):
+            ops._require_gpu(t)
+            if not t.is_contiguous():
+                raise ValueError("from_uint8: contiguous uint8 tensors expected")
+        if not model.x6mode and model.dtype == torch.bfloat16:
+            frames = torch.zeros((f, h, w, 8), dtype=torch.bfloat16, device=cmp.device)[..., :c]
+        else:
+            frames = torch.empty((f, h, w, c), dtype=torch.float32, device=cmp.device)
+        return cls(model, frames, chunk, graph, alpha, _u8=(cmp, bg, trimap))
+
+    def _ingest(self, k):
+        a, b = self.spans[k]
+        cmp, bg, tri = self._u8
+        ops.frames_from_u8(cmp[a:b], bg if bg.dim() == 3 or bg.shape[0] == 1 and cmp.shape[0] > 1 else bg[a:b],
+                           None if tri is None else tri[a:b], out=self.frames[a:b])
 
     def _slot(self, k):
         return None if self._slots is None else self._slots[k:k + 1]
@@ -84,6 +117,8 @@ class VideoMatter:
                 g.replay()
         else:
             for k, (a, b) in enumerate(self.spans):
+                if self._u8 is not None:
+                    self._ingest(k)
                 self.model.forward(self.frames[a:b], out=self.alpha[a:b], overflow=self._slot(k))
         if self._slots is not None:
             self.overflowed_chunks = [k for k, v in enumerate(self._slots.tolist()) if v]
