@@ -616,6 +616,28 @@ int vm_frames_from_u8(const uint8_t* cmp, const uint8_t* bg, const uint8_t* trim
  * 65535.f (bits 16, uint16 out); f32 product, ties to even, NaN -> 0. */
 int vm_matte_quantize(const float* alpha, long pixels, int bits, void* out, void* stream);
 
+/* The video model's feed in one pass: everything UNetSimple reads for the recurrence of train.py:346-366 at inference,
+ *   alpha[t] = create_model(cmp[t], bg[t], warp_img(alpha[t-1], backward[t]), phase False)   (unet_simple.py:148-152),
+ * from a decoded clip.  n, h, w are read from `cat`.
+ *   cmp        uint8 [n,h,w,3] BGR; bg uint8 [nb,h,w,3], nb == n or nb == 1 (one static plate); values
+ *              f32((double)u - VGG_MEAN[c]) as vm_frames_from_u8
+ *   prev_alpha f32 [n,h,w], backward f32 [n,h,w,2]: a = warp_img(prev_alpha, backward), bit-identical to
+ *              vm_remap_bilinear_f32 mode 0
+ *   forward    f32 [n,h,w,2] or NULL; when given, correct_alpha(backward, forward, a) per frame, bit-identical to
+ *              vm_fb_consistency (thresh, promote 0 / 1); *err_flag (device int, zeroed by the caller, required with
+ *              forward) is set where the reference raises IndexError, and the output is then undefined
+ *   towers     view [3n,h,w,3], VM_BF16 or VM_F32, cstride 8, coff 0, 16-byte aligned: frame t*n + i is tower t of
+ *              frame i; tower 0 = cmp, 1 = bg, 2 = [a, a, a]; channels 3..7 are written as zero
+ *   cat        view [n,h,w,9] of the same dtype, coff 0, cstride >= 16, 16-byte aligned pixels: channels 0..8 =
+ *              [cmp B,G,R, bg B,G,R, a, a, a], channels 9..15 are written as zero, channels from 16 on are not touched
+ *   warped     f32 [n,h,w] receiving a, or NULL (it must not alias prev_alpha)
+ * bf16 values are the round-to-nearest-even of the f32 values (what vm_convert_nhwc writes).  One pixel per thread:
+ * every output pixel is whole 16-byte stores, adjacent lanes write adjacent pixels, and the uint8 planes need no
+ * alignment.  No TF counterpart (feed_dict preprocessing + the loader's warp). */
+int vm_clip_feed(const uint8_t* cmp, const uint8_t* bg, int nb, const float* prev_alpha, const float* backward,
+                 const float* forward, float thresh, int promote, vm_tensor* towers, vm_tensor* cat, float* warped,
+                 int* err_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,10 +13,7 @@
 namespace vm {
 namespace {
 
-__device__ __forceinline__ double vgg_mean_d(int c) { return c == 0 ? 103.939 : c == 1 ? 116.779 : 123.68; }
-
-__device__ __forceinline__ float bgr_value(uint32_t u, int c) { return (float)((double)u - vgg_mean_d(c)); }
-
+// (bgr_value is in vm_common.h: vm_clip_feed in flow.hip feeds the same values)
 struct IngestArgs {
   const uint8_t* cmp;
   const uint8_t* bg;

@@ -139,6 +139,11 @@ struct Chunk<uint16_t> {
   }
 };
 
+// Decoded uint8 BGR -> the network's feed (loader.py:45,75-78): the mean is subtracted in float64 and the result is
+// rounded to f32 once.  One subtraction, no multiply-add pair: -ffp-contract does not change it.
+__device__ __forceinline__ double vgg_mean_d(int c) { return c == 0 ? 103.939 : c == 1 ? 116.779 : 123.68; }
+__device__ __forceinline__ float bgr_value(uint32_t u, int c) { return (float)((double)u - vgg_mean_d(c)); }
+
 __device__ __forceinline__ float act_apply(float v, int act) {
   if (act == VM_ACT_RELU) return v > 0.f ? v : 0.f;
   if (act == VM_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));

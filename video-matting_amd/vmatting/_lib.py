@@ -188,6 +188,8 @@ SIGNATURES = [
                            c_float, c_void_p]),
     ("vm_frames_from_u8", c_int, [c_void_p, c_void_p, c_void_p, c_int, P, c_void_p]),
     ("vm_matte_quantize", c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p]),
+    ("vm_clip_feed", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, P, P, c_void_p,
+                             c_void_p, c_void_p]),
 ]
 
 _lib = None

@@ -953,6 +953,54 @@ def matte_quantize(alpha, out=None, bits=8):
     return out
 
 
+def clip_feed(cmp, bg, prev_alpha, backward, forward=None, thresh=15.0, promote="numpy1", towers=None, cat=None,
+              warped=None, err=None):
+    """vm_clip_feed: the video model's feed in one pass.  cmp u8 [n,h,w,3] BGR, bg u8 [n,h,w,3] or one plate [h,w,3] /
+    [1,h,w,3], prev_alpha f32 [n,h,w] (or [n,h,w,1]), backward / forward f32 [n,h,w,2] (forward None: warp only) ->
+    ``towers`` (the [3n,h,w,3] view of a [3n,h,w,8] buffer: cmp, bg and [a,a,a] frames, a = warp_img(prev_alpha,
+    backward) [corrected by correct_alpha]) and ``cat`` (the [n,h,w,9] view of a buffer >= 16 channels wide), both in
+    the model's dtype — UNetSimple.feed_views returns the pair; ``warped`` f32 [n,h,w] optionally receives a.
+    With a forward flow, ``err`` (int32 [1], zeroed by the caller) is set where the reference raises IndexError; when
+    ``err`` is None the call keeps a flag of its own, waits for it and raises IndexError itself.  Returns warped."""
+    n, h, w, nb = _check_u8_frames(cmp, bg, None)
+    if promote not in ("numpy1", "numpy2"):
+        raise ValueError("clip_feed: promote must be 'numpy1' or 'numpy2', got %r" % (promote,))
+    for name, t, shapes in (("prev_alpha", prev_alpha, ((n, h, w), (n, h, w, 1))), ("backward", backward, ((n, h, w, 2),)),
+                            ("forward", forward, ((n, h, w, 2),)), ("warped", warped, ((n, h, w), (n, h, w, 1)))):
+        if t is None and name in ("forward", "warped"):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError("clip_feed: %s must be a float32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+        if tuple(t.shape) not in shapes:
+            raise ValueError("clip_feed: %s must be %s, got %s" % (name, list(shapes[0]), tuple(t.shape)))
+    if towers is None or cat is None:
+        raise ValueError("clip_feed: towers and cat views are required (UNetSimple.feed_views)")
+    if tuple(towers.shape) != (3 * n, h, w, 3) or tuple(cat.shape) != (n, h, w, 9):
+        raise ValueError("clip_feed: towers must be %s and cat %s, got %s and %s" %
+                         ((3 * n, h, w, 3), (n, h, w, 9), tuple(towers.shape), tuple(cat.shape)))
+    if towers.dtype != cat.dtype or cat.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("clip_feed: towers and cat are both f32 or both bf16, got %s and %s" % (towers.dtype, cat.dtype))
+    if err is not None and (not isinstance(err, torch.Tensor) or err.dtype != torch.int32 or err.numel() != 1):
+        raise TypeError("clip_feed: err must be an int32 tensor of one element")
+    for t in (cmp, bg, prev_alpha, backward, forward, towers, cat, warped, err):
+        if t is not None:
+            _require_gpu(t)
+    for t in (cmp, bg, prev_alpha, backward, forward, warped):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("clip_feed: contiguous frames, mattes and flows expected")
+    own = forward is not None and err is None
+    if own:
+        err = torch.zeros(1, dtype=torch.int32, device=cmp.device)
+    tv, cv = nhwc(towers), nhwc(cat)
+    check(lib().vm_clip_feed(_ptr(cmp), _ptr(bg), nb, _ptr(prev_alpha), _ptr(backward), _ptr(forward), float(thresh),
+                             0 if promote == "numpy1" else 1, ctypes.byref(tv), ctypes.byref(cv), _ptr(warped),
+                             _ptr(err), stream_handle()), "clip_feed")
+    if own and int(err.item()) != 0:
+        raise IndexError("clip_feed: a backward-flow target lies more than one frame outside the image "
+                         "(the reference's numpy IndexError, flow.py:46)")
+    return warped
+
+
 # ---------------------------------------------------------------- training step (train.py:288-343, config 5)
 
 def matting_loss_backward(pred, gt, raw_fg, in_bg, in_cmp, out=None):

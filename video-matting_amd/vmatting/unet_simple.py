@@ -121,12 +121,14 @@ class UNetSimple:
         for k, pc in self.padded.items():
             pc.bias = self.convs[k].bias
 
-    def _towers(self, b, splitk=True):
+    def _towers(self, b, splitk=True, frames=None):
         """The three frozen towers of create_model (vgg1/2/3 on cmp/bg/diff, unet_simple.py:57-89, 148-152) as one
         batch-3n VGG16 pass over b['tin'] (the towers share weights); 2x2 pools fused into the conv epilogue.
         ``splitk``: split-K on the small L4/L5 grids (training); inference leaves it off so frames are
-        batch-invariant."""
+        batch-invariant.  ``frames``: a slice of the tower-major batch to run instead of all of it (forward_fed)."""
         V = self.vgg.convs
+        if frames is not None:
+            b = {k: v[frames] for k, v in b.items() if k == "tin" or k.startswith("t_") or k.startswith("tpool")}
         t = lambda k: b["t_" + k]  # noqa: E731
         # conv1_1 -> conv1_2 -> pool1 as one strip-walking kernel that also writes conv1_1 (select1_2 reads it)
         ops.conv_pair_first(b["tin"][..., :3], V["conv1_1"], V["conv1_2"], "relu", out=t("conv1_2"),
@@ -167,10 +169,15 @@ class UNetSimple:
         xs = [t.to(self.device, torch.float32) for t in xs]
         n, h, w, _ = xs[0].shape
         b = self._buffers(n, h, w)
-        L = _levels(h, w)
-        C, B = self.convs, self.bn
         self.load_inputs(b, xs)
         self._towers(b, splitk=ph)
+        return self._decode(b, h, w, ph)
+
+    def _decode(self, b, h, w, ph):
+        """create_model after the towers (unet_simple.py:153-171): the select convs, the four upconv levels, the
+        output conv and its sigmoid, over the buffers ``b``."""
+        L = _levels(h, w)
+        C, B = self.convs, self.bn
         R = lambda x, k, out: conv_bn(*self.conv(k, x)[::-1], B[k], ph, "relu", out)  # noqa: E731
         # level 4
         for i in range(3):
@@ -224,6 +231,98 @@ class UNetSimple:
         self.upconv1, self.conv1 = b["up1n"][..., :30], b["c1"]
         self.logits = b["logits"]
         self.output = b["out"]
+
+    # ------------------------------------------------------------------ inference on a clip (vmatting/clip.py)
+    def feed_views(self, n, h, w):
+        """The (towers, cat) views ops.clip_feed writes for an [n,h,w] batch: the [3n,h,w,3] view of the towers' input
+        batch (8 channels wide) and the [n,h,w,9] view of the level-0 concat (32 channels wide)."""
+        b = self._buffers(n, h, w)
+        return b["tin"][..., :3], b["in9"][..., :9]
+
+    def forward_fed(self, n, h, w, towers=(0, 1, 2)):
+        """``forward`` after load_inputs, with phase False, on what ops.clip_feed left in the feed_views buffers.
+        ``towers``: the towers whose VGG pass runs, each run of adjacent towers as one batch; a tower left out keeps
+        the feature maps of the call that last ran it (a static background plate: tower 1 once per clip)."""
+        towers = tuple(sorted(set(int(t) for t in towers)))
+        if not towers or towers[0] < 0 or towers[-1] > 2:
+            raise ValueError("forward_fed: towers is a non-empty subset of (0, 1, 2), got %r" % (towers,))
+        b = self._buffers(n, h, w)
+        if towers == (0, 1, 2):
+            self._towers(b, splitk=False)
+        else:
+            runs = [[towers[0], towers[0] + 1]]
+            for t in towers[1:]:
+                if t == runs[-1][1]:
+                    runs[-1][1] = t + 1
+                else:
+                    runs.append([t, t + 1])
+            for lo, hi in runs:
+                self._towers(b, splitk=False, frames=slice(lo * n, hi * n))
+        return self._decode(b, h, w, False)
+
+    def capture_fed(self, n, h, w, towers=(0, 1, 2), pre=None, post=None):
+        """Record forward_fed(n, h, w, towers) into a HIP graph over the model's static buffers, with ``pre`` /
+        ``post`` (callables that only launch work on the current stream: the feed before it, the quantisation and the
+        download after it) recorded into the same graph, as UNet.capture(static=True, pre=, post=) does.  One linear
+        chain on the capturing stream: no fork, no join.  Returns a GraphedFed; the weights and buffers are the ones
+        captured, so load_params or a forward at another shape comes before the capture, not after it."""
+        return GraphedFed(self, n, h, w, towers, pre, post)
+
+    def load_params(self, conv, bn=None):
+        """The inference hand-off of VideoTrainer.params_numpy(): ``conv`` {scope: (w, b|None)} re-packed into this
+        model's convs (and their channel-padded packs), ``bn`` {scope: (gamma, beta)} set per scope.  Graphs
+        captured before this call keep the old weights."""
+        missing = [k for k, _, _ in NEW_CONVS if k not in conv]
+        if missing:
+            raise ValueError("load_params: no parameters for %s" % ", ".join(missing))
+        for k, cin, cout in NEW_CONVS:
+            if tuple(np.shape(conv[k][0])) != (3, 3, cin, cout):
+                raise ValueError("load_params: %s is [3,3,%d,%d], got %s" % (k, cin, cout, np.shape(conv[k][0])))
+        for k in (bn or {}):
+            if k not in self.bn:
+                raise ValueError("load_params: no batch-norm scope %r" % (k,))
+        self.params = {k: (np.asarray(conv[k][0], np.float32),
+                           None if conv[k][1] is None else np.asarray(conv[k][1], np.float32)) for k, _, _ in NEW_CONVS}
+        self.convs = {k: ops.PackedConv(w, b, self.dtype, self.device) for k, (w, b) in self.params.items()}
+        if self.dtype == torch.bfloat16:
+            self.padded = {k: ops.PackedConv.from_source(self.convs[k], c, self.convs[k].cout, self.dtype,
+                                                         bias=self.convs[k].bias) for k, c in CIN_PAD.items()}
+        for k, (gamma, beta) in (bn or {}).items():
+            self.bn[k].set(gamma, beta)
+        return self
+
+
+class GraphedFed:
+    """UNetSimple.capture_fed's result: ``replay()`` launches the recorded pre -> forward_fed -> post chain on the
+    current stream; ``output`` is the model's static f32 alpha buffer [n,h,w,1]."""
+
+    def __init__(self, model, n, h, w, towers=(0, 1, 2), pre=None, post=None):
+        self.model = model
+        dev = model.device
+
+        def run():
+            if pre is not None:
+                pre()
+            o = model.forward_fed(n, h, w, towers)
+            if post is not None:
+                post()
+            return o
+        b = model._buffers(n, h, w)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):  # lazily built workspaces and kernel attributes, before the capture
+            run()
+        main = torch.cuda.current_stream(dev)
+        main.wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.output = run()
+        self._ws = b  # the buffers the graph reads and writes stay alive with it
+
+    def replay(self):
+        self.graph.replay()
+        return self.output
 
 
 def create_model(cmp, bg, diff, phase, vgg16_npy_path=None, dtype="bf16", device="cuda", params=None):
