@@ -23,38 +23,27 @@ import numpy as np
 import torch
 
 from . import ops
-from .stream import OUT_DTYPES
+from .pipeline import Slot, SlotPipeline, check_out, check_static_bg
 from .unet_simple import UNetSimple
 
 PROMOTE = ("numpy1", "numpy2")
 
 
-class _Slot:
+class _Slot(Slot):
     """One frame in flight: pinned host inputs, their device copies, the quantised matte, the pinned output, the
     IndexError flag with its pinned copy, the two events and the slot's graphs (by the towers they run)."""
 
     def __init__(self, cs):
-        dev, h, w = cs.device, cs.h, cs.w
-        pin = lambda shape, dt: torch.zeros(shape, dtype=dt).pin_memory()  # noqa: E731
-        gpu = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-        self.h_cmp, self.d_cmp = pin((1, h, w, 3), torch.uint8), gpu((1, h, w, 3), torch.uint8)
-        self.h_bg = self.d_bg = self.h_fw = self.d_fw = None
-        if cs.static_bg is None:
-            self.h_bg, self.d_bg = pin((1, h, w, 3), torch.uint8), gpu((1, h, w, 3), torch.uint8)
-        self.h_bw, self.d_bw = pin((1, h, w, 2), torch.float32), gpu((1, h, w, 2), torch.float32)
-        if cs.occlusion:
-            self.h_fw, self.d_fw = pin((1, h, w, 2), torch.float32), gpu((1, h, w, 2), torch.float32)
-        _, t_dt, _ = OUT_DTYPES[cs.out]
-        self.q = None if t_dt is None else gpu((1, h, w), t_dt)
-        self.h_out = pin((1, h, w), t_dt or torch.float32)
-        self.flag = gpu((1,), torch.int32)
-        self.h_flag = pin((1,), torch.int32)
-        self.uploaded, self.done = torch.cuda.Event(), torch.cuda.Event()
+        h, w = cs.h, cs.w
+        super().__init__(cs.device, (("cmp", (1, h, w, 3), torch.uint8),
+                                     ("bw", (1, h, w, 2), torch.float32),
+                                     ("bg", (1, h, w, 3) if cs.static_bg is None else None, torch.uint8),
+                                     ("fw", (1, h, w, 2) if cs.occlusion else None, torch.float32)),
+                         1, h, w, cs.out, flag=cs.occlusion)
         self.graphs = {}
-        self.index = 0  # the frame in flight
 
 
-class ClipStream:
+class ClipStream(SlotPipeline):
     """``ClipStream(model, h, w, ...).run(source, alpha0)`` yields one [h,w] numpy matte per item of ``source``, in
     order.
 
@@ -87,29 +76,20 @@ class ClipStream:
         h, w, depth = int(h), int(w), int(depth)
         if h < 1 or w < 1 or depth < 1:
             raise ValueError("ClipStream: h, w and depth must be positive (got %d, %d, %d)" % (h, w, depth))
-        if out not in OUT_DTYPES:
-            raise ValueError("ClipStream: out must be one of %s, got %r" % (sorted(OUT_DTYPES), out))
+        check_out("ClipStream", out)
         if promote not in PROMOTE:
             raise ValueError("ClipStream: promote must be one of %s, got %r" % (PROMOTE, promote))
         thresh = float(thresh)
         if not thresh >= 0.0:
             raise ValueError("ClipStream: thresh must be a non-negative number, got %r" % (thresh,))
-        if static_bg is not None:
-            static_bg = np.asarray(static_bg)
-            if static_bg.dtype != np.uint8:
-                raise TypeError("ClipStream: static_bg must be uint8, got %s" % static_bg.dtype)
-            if static_bg.shape != (h, w, 3):
-                raise ValueError("ClipStream: static_bg must be [h,w,3] = %s, got %s" % ((h, w, 3), static_bg.shape))
-            static_bg = np.ascontiguousarray(static_bg)
+        static_bg = check_static_bg("ClipStream", static_bg, h, w)
         self.model, self.h, self.w, self.depth = model, h, w, depth
         self.static_bg, self.occlusion, self.thresh, self.promote = static_bg, bool(occlusion), thresh, promote
         self.out, self.graph = out, bool(graph)
         self.reuse_bg_tower = bool(reuse_bg_tower) and static_bg is not None
         self.device = model.device
         self.stats = {"bg_tower_evals": 0, "frames": 0}
-        self._slots = None   # built with the first valid item: nothing touches the device before that
         self._plate = self._buf = None
-        self._upload = self._compute = None
 
     # ------------------------------------------------------------------ checks (host only)
     def check_item(self, item):
@@ -153,7 +133,7 @@ class ClipStream:
         """Streams, slots and (graph=True) every slot's graphs.  The graphs are captured here, before alpha0 is in
         place: a capture runs its chain once to warm up, which overwrites the model's output buffer."""
         dev = self.device
-        self._upload, self._compute = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+        self._make_streams()
         self._buf = self.model._buffers(1, self.h, self.w)
         self._views = self.model.feed_views(1, self.h, self.w)
         self._alpha = self._buf["out"]
@@ -166,40 +146,31 @@ class ClipStream:
                 for i, s in enumerate(self._slots):
                     for towers in sorted({self._towers_of(j) for j in range(i, i + 2 * self.depth, self.depth)}):
                         s.graphs[towers] = self.model.capture_fed(
-                            1, self.h, self.w, towers, pre=lambda s=s: self._feed(s), post=lambda s=s: self._finish(s))
+                            1, self.h, self.w, towers, pre=lambda s=s: self._feed(s),
+                            post=lambda s=s: s.download(self._alpha))
             torch.cuda.synchronize(dev)
 
+    def _needs_setup(self):  # (again when the model ran another shape since: its buffers were replaced)
+        return self._slots is None or self.model._buffers(1, self.h, self.w) is not self._buf
+
+    def _begin(self):  # what the caller queued comes first; then the matte before the first frame
+        super()._begin()
+        with torch.cuda.stream(self._compute):
+            self._alpha.copy_(torch.from_numpy(self._alpha0).view(1, self.h, self.w, 1))
+
     def _feed(self, s):
-        if self.occlusion:
+        if s.flag is not None:
             s.flag.zero_()
         towers, cat = self._views
         ops.clip_feed(s.d_cmp, self._plate if self._plate is not None else s.d_bg, self._alpha, s.d_bw, s.d_fw,
                       self.thresh, self.promote, towers=towers, cat=cat, err=s.flag)
 
-    def _finish(self, s):
-        if s.q is None:
-            s.h_out.copy_(self._alpha[:, :, :, 0], non_blocking=True)
-        else:
-            ops.matte_quantize(self._alpha, out=s.q, bits=OUT_DTYPES[self.out][2])
-            s.h_out.copy_(s.q, non_blocking=True)
-        if self.occlusion:
-            s.h_flag.copy_(s.flag, non_blocking=True)
-
     def _submit(self, s, index, cmp, bg, bw, fw):
         s.index = index
-        s.h_cmp[0].numpy()[...] = cmp
-        s.h_bw[0].numpy()[...] = bw
-        if bg is not None:
-            s.h_bg[0].numpy()[...] = bg
-        if fw is not None:
-            s.h_fw[0].numpy()[...] = fw
+        for name, a in (("cmp", cmp), ("bw", bw), ("bg", bg), ("fw", fw)):
+            s.stage(name, a, 1)
         with torch.cuda.stream(self._upload):
-            s.d_cmp.copy_(s.h_cmp, non_blocking=True)
-            s.d_bw.copy_(s.h_bw, non_blocking=True)
-            if bg is not None:
-                s.d_bg.copy_(s.h_bg, non_blocking=True)
-            if fw is not None:
-                s.d_fw.copy_(s.h_fw, non_blocking=True)
+            s.upload(1)
             s.uploaded.record(self._upload)
         towers = self._towers_of(index)
         self.stats["frames"] += 1
@@ -211,50 +182,18 @@ class ClipStream:
             else:
                 self._feed(s)
                 self.model.forward_fed(1, self.h, self.w, towers)
-                self._finish(s)
+                s.download(self._alpha)
             s.done.record(self._compute)
 
     def _retire(self, s):
         s.done.synchronize()
-        if self.occlusion and int(s.h_flag[0]):
+        if s.h_flag is not None and int(s.h_flag[0]):
             raise IndexError("ClipStream: frame %d: a backward-flow target lies more than one frame outside the image "
                              "(the reference's numpy IndexError, flow.py:46)" % s.index)
         return s.h_out[0].numpy().copy()
 
     def run(self, source, alpha0):
         """Generator: one [h,w] matte (numpy, the ``out`` dtype) per source item, in source order."""
-        alpha0 = self.check_alpha0(alpha0)
+        self._alpha0 = self.check_alpha0(alpha0)
         self.stats = {"bg_tower_evals": 0, "frames": 0}
-        inflight, error, index = [], None, 0
-        it = iter(source)
-        try:
-            while True:
-                try:
-                    item = next(it)
-                    cmp, bg, bw, fw = self.check_item(item)
-                except StopIteration:
-                    break
-                except Exception as e:  # the source failed or yielded a bad item: finish what was taken, then raise
-                    error = e
-                    break
-                if self._slots is None or self.model._buffers(1, self.h, self.w) is not self._buf:
-                    self._setup()  # (again when the model ran another shape since: its buffers were replaced)
-                if index == 0:  # what the caller queued comes first; then the matte before the first frame
-                    self._compute.wait_stream(torch.cuda.current_stream(self.device))
-                    with torch.cuda.stream(self._compute):
-                        self._alpha.copy_(torch.from_numpy(alpha0).view(1, self.h, self.w, 1))
-                s = self._slots[index % self.depth]
-                self._submit(s, index, cmp, bg, bw, fw)
-                index += 1
-                inflight.append(s)
-                if len(inflight) >= self.depth:
-                    yield self._retire(inflight.pop(0))
-            while inflight:
-                yield self._retire(inflight.pop(0))
-        finally:
-            # also when the consumer abandons the generator or a frame raised IndexError: nothing stays queued
-            if self._slots is not None:
-                self._upload.synchronize()
-                self._compute.synchronize()
-        if error is not None:
-            raise error
+        yield from super().run(source)

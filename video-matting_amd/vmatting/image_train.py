@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import ops, parallel
-from .train import TrainerBase
+from .train import TrainerBase, TrainGraphBase, _to_device_f32
 from .unet import UNetImage, _levels
 
 # build order of unet.py:96-143 (the TF variable creation order): scope, keeps a bias
@@ -170,9 +170,7 @@ class ImageTrainer(TrainerBase):
     # ------------------------------------------------------------------------------------------- forward
     def forward(self, cmp, bg):
         """UNetImage(x = concat(cmp, bg)).output (unet.py:86-145) -> alpha [N,H,W,1] f32."""
-        dev = lambda t: (t if isinstance(t, torch.Tensor) else torch.from_numpy(  # noqa: E731
-            np.ascontiguousarray(t, np.float32))).to(self.device, torch.float32)
-        cmp, bg = dev(cmp), dev(bg)
+        cmp, bg = _to_device_f32(cmp, self.device), _to_device_f32(bg, self.device)
         n, h, w, c = cmp.shape
         if c != 3 or tuple(bg.shape) != (n, h, w, 3):
             raise ValueError("ImageTrainer expects cmp, bg of 3 channels each (train.py:116: x = [cmp, bg])")
@@ -276,18 +274,11 @@ class ImageTrainer(TrainerBase):
         self._relu_conv_backward("conv1_1", g["dc11"], b["c11"], b["in8"][..., :6], "dz11")
 
     # ------------------------------------------------------------------------------------------- step
-    def step(self, cmp, bg, gt, raw_fg):
-        """One training iteration; returns a new device tensor [loss, alpha_loss, compositional_loss] (pre-update)."""
-        self.forward(cmp, bg)
-        dev = lambda t: (t if isinstance(t, torch.Tensor) else torch.from_numpy(  # noqa: E731
-            np.ascontiguousarray(t, np.float32))).to(self.device, torch.float32).contiguous()
-        gt, raw_fg, bg_d, cmp_d = dev(gt), dev(raw_fg), dev(bg), dev(cmp)
-        g = self._g
-        g["loss"].copy_(ops.matting_loss(self.model.output, gt, raw_fg, bg_d, cmp_d))
-        self.grad.zero_()
-        self.backward(gt, raw_fg, bg_d, cmp_d)
-        self.apply_gradients()
-        return g["loss"].clone()
+    def _bufs(self):
+        return self._g
+
+    def _graph_tensors(self):
+        return list(self._g.values()) + list(self.model._ws.values())
 
     def capture(self, cmp, bg, gt, raw_fg):
         """Record one step's forward + loss and its backward as two HIP graphs -> ImageTrainGraph (DDP exchange +
@@ -306,61 +297,15 @@ class ImageTrainer(TrainerBase):
         return fwd, fwd + (fwd - c11)
 
 
-class ImageTrainGraph:
+class ImageTrainGraph(TrainGraphBase):
     """ImageTrainer.capture's result: ``step(cmp, bg, gt, raw_fg)`` = ImageTrainer.step on graph replays."""
 
-    def __init__(self, trn, *batch):
-        dev = trn.device
-        self.trn = trn
-        self.inputs = [(t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t, np.float32)))
-                       .to(dev, torch.float32).contiguous().clone() for t in batch]
+    def _capture(self):
         # captured without the trainer's side stream: a HIP-graph replay on ROCm 7 ran the fork's branches one after
         # the other and the fork cost time (6.7 ms against 6.5 on one stream; eager with the side stream 6.0)
+        trn = self.trn
         self._side, trn._side = trn._side, None
         try:
-            self._capture(trn, dev)
+            return super()._capture()
         finally:
             trn._side = self._side
-
-    def _capture(self, trn, dev):
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):  # buffers and workspaces before capture
-            self._forward()
-            self._backward()
-        main = torch.cuda.current_stream(dev)
-        main.wait_stream(side)
-        torch.cuda.synchronize(dev)
-        for d in (trn._g, trn.model._ws):  # allocated on the side stream, replayed on this one
-            for t in d.values():
-                t.record_stream(main)
-        for t in ops._ws_cache.values():
-            t.record_stream(main)
-        self.g_fwd, self.g_bwd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_fwd):
-            self._forward()
-        with torch.cuda.graph(self.g_bwd):
-            self._backward()
-
-    def _forward(self):
-        cmp, bg, gt, fg = self.inputs
-        t = self.trn
-        t.forward(cmp, bg)
-        t._g["loss"].copy_(ops.matting_loss(t.model.output, gt, fg, bg, cmp))
-
-    def _backward(self):
-        cmp, bg, gt, fg = self.inputs
-        self.trn.grad.zero_()
-        self.trn.backward(gt, fg, bg, cmp)
-
-    def load(self, *batch):
-        for dst, src in zip(self.inputs, batch):
-            dst.copy_(src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src, np.float32)))
-
-    def step(self, *batch):
-        if batch:
-            self.load(*batch)
-        self.g_fwd.replay()
-        self.g_bwd.replay()
-        self.trn.apply_gradients()
-        return self.trn._g["loss"].clone()

@@ -907,6 +907,16 @@ def _check_u8_frames(cmp, bg, trimap):
     return n, h, w, (n if tuple(bg.shape) == (n, h, w, 3) else 1)
 
 
+def frame_buffer(model, n, h, w, native=None):
+    """An [n,h,w,IN_CH] input-frame buffer for ``model``: ``native`` (default: a plain bf16 model) gives bf16 pixels 8
+    channels wide, the pad zeroed once, which the forward reads in place; otherwise f32."""
+    if native is None:
+        native = not model.x6mode and model.dtype == torch.bfloat16
+    if native:
+        return torch.zeros((n, h, w, 8), dtype=torch.bfloat16, device=model.device)[..., :model.IN_CH]
+    return torch.empty((n, h, w, model.IN_CH), dtype=torch.float32, device=model.device)
+
+
 def frames_from_u8(cmp, bg, trimap=None, out=None, dtype=torch.float32):
     """vm_frames_from_u8: decoded uint8 frames -> the network input in one pass.  cmp u8 [n,h,w,3] BGR, bg u8
     [n,h,w,3] or one static plate [h,w,3] / [1,h,w,3], trimap u8 [n,h,w] or None -> ``out`` [n,h,w,C] (C = 7 with a

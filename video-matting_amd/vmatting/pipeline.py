@@ -1,0 +1,144 @@
+"""The slot pipeline the streamed paths share (stream.FrameStream, clip.ClipStream): items of a host source move
+through ``depth`` slots, the upload of item i + 1 on one stream beside the compute of item i on another, and results
+come back in order, ``depth - 1`` items behind the source.
+
+SlotPipeline owns the generator; a streamed path supplies the hooks.  Slot holds what one item in flight needs: pinned
+host / device buffer pairs, the quantised output and its pinned copy, an optional int32 flag pair and two events.
+"""
+
+import numpy as np
+import torch
+
+from . import ops
+
+OUT_DTYPES = {"u8": (np.uint8, torch.uint8, 8), "u16": (np.uint16, torch.uint16, 16), "f32": (np.float32, None, 0)}
+
+
+def check_out(who, out):
+    if out not in OUT_DTYPES:
+        raise ValueError("%s: out must be one of %s, got %r" % (who, sorted(OUT_DTYPES), out))
+    return out
+
+
+def check_static_bg(who, static_bg, h, w):
+    """``static_bg`` as a contiguous uint8 [h,w,3] array (None stays None)."""
+    if static_bg is None:
+        return None
+    static_bg = np.asarray(static_bg)
+    if static_bg.dtype != np.uint8:
+        raise TypeError("%s: static_bg must be uint8, got %s" % (who, static_bg.dtype))
+    if static_bg.shape != (h, w, 3):
+        raise ValueError("%s: static_bg must be [h,w,3] = %s, got %s" % (who, (h, w, 3), static_bg.shape))
+    return np.ascontiguousarray(static_bg)
+
+
+class Slot:
+    """One item in flight.  ``pairs``: (name, shape | None, dtype) per input; each gives a pinned ``h_<name>`` and its
+    device copy ``d_<name>`` (both None for a None shape: an input this configuration does not take).  ``q`` [n,h,w]
+    is the quantised matte (None for out="f32") and ``h_out`` its pinned copy; ``flag`` / ``h_flag`` an int32 [1] pair
+    (None without ``flag``); ``uploaded`` / ``done`` the events of the item's upload and of its compute chain."""
+
+    def __init__(self, device, pairs, n, h, w, out, flag):
+        pin = lambda shape, dt: torch.zeros(shape, dtype=dt).pin_memory()  # noqa: E731
+        gpu = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)  # noqa: E731
+        self._names = [name for name, shape, _ in pairs if shape is not None]
+        for name, shape, dt in pairs:
+            setattr(self, "h_" + name, None if shape is None else pin(shape, dt))
+            setattr(self, "d_" + name, None if shape is None else gpu(shape, dt))
+        _, t_dt, self._bits = OUT_DTYPES[out]
+        self.q = None if t_dt is None else gpu((n, h, w), t_dt)
+        self.h_out = pin((n, h, w), t_dt or torch.float32)
+        self.flag = gpu((1,), torch.int32) if flag else None
+        self.h_flag = pin((1,), torch.int32) if flag else None
+        self.uploaded, self.done = torch.cuda.Event(), torch.cuda.Event()
+        self.index = 0  # the item in flight: its position in the source
+
+    def stage(self, name, array, k):
+        """Copy a host array into the first k frames of the pinned buffer (None: an input not taken)."""
+        if array is not None:
+            getattr(self, "h_" + name)[:k].numpy()[...] = array
+
+    def upload(self, k):
+        """Queue the first k frames of every pinned input to its device copy, on the current stream."""
+        for name in self._names:
+            getattr(self, "d_" + name)[:k].copy_(getattr(self, "h_" + name)[:k], non_blocking=True)
+
+    def download(self, alpha):
+        """Quantise ``alpha`` ([k,h,w,1] f32) and queue it, and the flag, to the pinned outputs, on the current
+        stream."""
+        k = alpha.shape[0]
+        if self.q is None:
+            self.h_out[:k].copy_(alpha[:, :, :, 0], non_blocking=True)
+        else:
+            ops.matte_quantize(alpha, out=self.q[:k], bits=self._bits)
+            self.h_out[:k].copy_(self.q[:k], non_blocking=True)
+        if self.flag is not None:
+            self.h_flag.copy_(self.flag, non_blocking=True)
+
+
+class SlotPipeline:
+    """``run(source)`` over the hooks of a streamed path:
+
+    check_item(item) -> args   host-only validation of one source item, before any device work for it
+    _needs_setup()             True until _setup() has built ``_slots`` (a list of ``depth`` slots)
+    _setup()                   streams (_make_streams), slots and whatever else the first valid item needs
+    _begin()                   before the first item of a run is submitted; here: the compute stream waits on what
+                               the caller queued
+    _submit(slot, index, *args) stage, upload and queue the compute chain of one item
+    _retire(slot) -> result    wait for the slot's chain; the host result
+    _drain()                   nothing stays queued on the slots: both streams synchronised
+    """
+
+    device = None
+    depth = 1
+    _slots = None   # built with the first valid item: nothing touches the device before that
+    _upload = _compute = None
+
+    def check_item(self, item):
+        raise NotImplementedError
+
+    def _needs_setup(self):
+        return self._slots is None
+
+    def _make_streams(self):
+        self._upload, self._compute = torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device)
+
+    def _begin(self):
+        self._compute.wait_stream(torch.cuda.current_stream(self.device))
+
+    def _drain(self):
+        self._upload.synchronize()
+        self._compute.synchronize()
+
+    def run(self, source):
+        """Generator: one result per source item, in source order, ``depth - 1`` items behind the source.  If the
+        source raises or yields a bad item, what was taken is finished and yielded, then the exception propagates."""
+        inflight, error, index = [], None, 0
+        it = iter(source)
+        try:
+            while True:
+                try:
+                    args = self.check_item(next(it))
+                except StopIteration:
+                    break
+                except Exception as e:  # the source failed or yielded a bad item: finish what was taken, then raise
+                    error = e
+                    break
+                if self._needs_setup():
+                    self._setup()
+                if index == 0:
+                    self._begin()
+                s = self._slots[index % self.depth]
+                self._submit(s, index, *args)
+                index += 1
+                inflight.append(s)
+                if len(inflight) >= self.depth:
+                    yield self._retire(inflight.pop(0))
+            while inflight:
+                yield self._retire(inflight.pop(0))
+        finally:
+            # also when the consumer abandons the generator or _retire raises: nothing stays queued on the slots
+            if self._slots is not None:
+                self._drain()
+        if error is not None:
+            raise error

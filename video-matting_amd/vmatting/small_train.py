@@ -26,7 +26,7 @@ import torch
 from . import ops, parallel
 from .layers import EPS
 from .small import NEW_CONVS
-from .train import TrainerBase
+from .train import TrainerBase, TrainGraphBase, _to_device_f32
 from .weights import init_conv
 
 # batch-norm width per scope: new_conv's cout, upconv_concat's concat (small.py:20-22)
@@ -180,9 +180,7 @@ class SmallTrainer(TrainerBase):
 
     def forward(self, cmp, bg):
         """UNetSmall(concat(cmp, bg), phase=True).output (small.py:37-50) -> alpha [N,H,W,1] f32."""
-        dev = lambda t: (t if isinstance(t, torch.Tensor) else torch.from_numpy(  # noqa: E731
-            np.ascontiguousarray(t, np.float32))).to(self.device, torch.float32)
-        cmp, bg = dev(cmp), dev(bg)
+        cmp, bg = _to_device_f32(cmp, self.device), _to_device_f32(bg, self.device)
         n, h, w, c = cmp.shape
         if self.cin != 2 * c or tuple(bg.shape) != (n, h, w, c):
             raise ValueError("SmallTrainer(cin=%d) expects cmp, bg of %d channels each" % (self.cin, self.cin // 2))
@@ -256,18 +254,8 @@ class SmallTrainer(TrainerBase):
         self._conv_backward("conv1_1", b["inp"][..., :self.cin], b["da11"], b["cat2"][..., :8])
 
     # ------------------------------------------------------------------------------------------- step
-    def step(self, cmp, bg, gt, raw_fg):
-        """One training iteration; returns a new device tensor [loss, alpha_loss, compositional_loss] (pre-update)."""
-        self.forward(cmp, bg)
-        dev = lambda t: (t if isinstance(t, torch.Tensor) else torch.from_numpy(  # noqa: E731
-            np.ascontiguousarray(t, np.float32))).to(self.device, torch.float32).contiguous()
-        gt, raw_fg, bg_d, cmp_d = dev(gt), dev(raw_fg), dev(bg), dev(cmp)
-        b = self._b
-        b["loss"].copy_(ops.matting_loss(b["alpha"], gt, raw_fg, bg_d, cmp_d))
-        self.grad.zero_()
-        self.backward(gt, raw_fg, bg_d, cmp_d)
-        self.apply_gradients()
-        return b["loss"].clone()
+    def _bufs(self):
+        return self._b
 
     def capture(self, cmp, bg, gt, raw_fg):
         """Record one step's forward + loss and its backward as two HIP graphs (torch.cuda.CUDAGraph over the same
@@ -284,52 +272,10 @@ class SmallTrainer(TrainerBase):
         return conv, bn
 
 
-class SmallTrainGraph:
+class SmallTrainGraph(TrainGraphBase):
     """SmallTrainer.capture's result: ``step(cmp, bg, gt, raw_fg)`` = SmallTrainer.step on graph replays."""
 
     def __init__(self, trn, *batch):
         if trn.sync_bn and torch.distributed.get_backend() != "nccl":
             raise NotImplementedError("capture with sync_bn needs the nccl (RCCL) backend")
-        dev = trn.device
-        self.trn = trn
-        self.inputs = [(t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t, np.float32)))
-                       .to(dev, torch.float32).contiguous().clone() for t in batch]
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):  # buffers, workspaces and the SyncBN batch count before capture
-            self._forward()
-            self._backward()
-        main = torch.cuda.current_stream(dev)
-        main.wait_stream(side)
-        torch.cuda.synchronize(dev)
-        for t in trn._b.values():  # allocated on the side stream, replayed on this one
-            for u in (t if isinstance(t, tuple) else (t,)):
-                u.record_stream(main)
-        self.g_fwd, self.g_bwd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_fwd):
-            self._forward()
-        with torch.cuda.graph(self.g_bwd):
-            self._backward()
-
-    def _forward(self):
-        cmp, bg, gt, fg = self.inputs
-        t = self.trn
-        t.forward(cmp, bg)
-        t._b["loss"].copy_(ops.matting_loss(t._b["alpha"], gt, fg, bg, cmp))
-
-    def _backward(self):
-        cmp, bg, gt, fg = self.inputs
-        self.trn.grad.zero_()
-        self.trn.backward(gt, fg, bg, cmp)
-
-    def load(self, *batch):
-        for dst, src in zip(self.inputs, batch):
-            dst.copy_(src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src, np.float32)))
-
-    def step(self, *batch):
-        if batch:
-            self.load(*batch)
-        self.g_fwd.replay()
-        self.g_bwd.replay()
-        self.trn.apply_gradients()
-        return self.trn._b["loss"].clone()
+        super().__init__(trn, *batch)

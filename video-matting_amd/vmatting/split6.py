@@ -188,3 +188,12 @@ class Split6Forward:
                 ops._ptr(alpha if k == 2 else None), ops.stream_handle()), "conv3x3_head_acc")
         self.logits = lg[2]
         return alpha
+
+
+def rerun_x6(owner, frames, out):
+    """A span of ``owner.model``'s frames again on bf16x6 (f32 range) into ``out``: what a streamed path does with a
+    chunk whose f16x3 forward left fp16's range.  ``owner._x6``, the bf16x6 forward of the same parameters, is built
+    on first use (it reads the model's parameters only)."""
+    if owner._x6 is None:
+        owner._x6 = Split6Forward(owner.model)
+    return owner._x6.forward(frames, out=out)

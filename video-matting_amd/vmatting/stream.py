@@ -20,44 +20,28 @@ import numpy as np
 import torch
 
 from . import ops
+from .pipeline import OUT_DTYPES, Slot, SlotPipeline, check_out, check_static_bg  # noqa: F401  (OUT_DTYPES: public)
+from .split6 import rerun_x6
 
-OUT_DTYPES = {"u8": (np.uint8, torch.uint8, 8), "u16": (np.uint16, torch.uint16, 16), "f32": (np.float32, None, 0)}
 
-
-class _Slot:
+class _Slot(Slot):
     """One chunk in flight: pinned host inputs, their device copies, the frame buffer in the model's input format,
     the f32 alpha, the quantised matte, the pinned output and the two events."""
 
     def __init__(self, fs):
-        dev, n, h, w, c = fs.device, fs.chunk, fs.h, fs.w, fs.model.IN_CH
-        pin = lambda shape, dt: torch.empty(shape, dtype=dt).pin_memory()  # noqa: E731
-        gpu = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
-        self.h_cmp, self.d_cmp = pin((n, h, w, 3), torch.uint8), gpu((n, h, w, 3), torch.uint8)
-        self.h_bg = self.d_bg = self.h_tri = self.d_tri = None
-        if fs.static_bg is None:
-            self.h_bg, self.d_bg = pin((n, h, w, 3), torch.uint8), gpu((n, h, w, 3), torch.uint8)
-        if fs.trimap:
-            self.h_tri, self.d_tri = pin((n, h, w), torch.uint8), gpu((n, h, w), torch.uint8)
-        if fs.native:
-            self.frames = torch.zeros((n, h, w, 8), dtype=torch.bfloat16, device=dev)[..., :c]
-        else:
-            self.frames = gpu((n, h, w, c), torch.float32)
-        self.alpha = gpu((n, h, w, 1), torch.float32)
-        np_dt, t_dt, _ = OUT_DTYPES[fs.out]
-        self.q = None if t_dt is None else gpu((n, h, w), t_dt)
-        self.h_out = pin((n, h, w), t_dt or torch.float32)
-        # f16x3: this slot's range flag and its pinned copy, downloaded with the matte
-        self.flag = self.h_flag = None
-        if fs.model.split_mode == "f16x3":
-            self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.h_flag = torch.zeros(1, dtype=torch.int32).pin_memory()
-        self.uploaded, self.done = torch.cuda.Event(), torch.cuda.Event()
+        n, h, w = fs.chunk, fs.h, fs.w
+        u8 = torch.uint8
+        super().__init__(fs.device, (("cmp", (n, h, w, 3), u8),
+                                     ("bg", (n, h, w, 3) if fs.static_bg is None else None, u8),
+                                     ("tri", (n, h, w) if fs.trimap else None, u8)),
+                         n, h, w, fs.out, flag=fs.model.split_mode == "f16x3")  # f16x3: this slot's range flag
+        self.frames = ops.frame_buffer(fs.model, n, h, w)
+        self.alpha = torch.empty((n, h, w, 1), dtype=torch.float32, device=fs.device)
         self.graph = None
         self.k = 0       # frames of the chunk in flight
-        self.index = 0   # its position in the source
 
 
-class FrameStream:
+class FrameStream(SlotPipeline):
     """``FrameStream(model, h, w, ...).run(source)`` yields one [k,h,w] numpy matte per item of ``source``, in order.
 
     ``source`` yields ``(cmp, bg, trimap)``: uint8 numpy arrays [k,h,w,3], [k,h,w,3] | None, [k,h,w] | None with
@@ -75,27 +59,17 @@ class FrameStream:
         if h < 1 or w < 1 or chunk < 1 or depth < 1:
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
                              (h, w, chunk, depth))
-        if out not in OUT_DTYPES:
-            raise ValueError("FrameStream: out must be one of %s, got %r" % (sorted(OUT_DTYPES), out))
+        check_out("FrameStream", out)
         if (7 if trimap else 6) != model.IN_CH:
             raise ValueError("FrameStream: %s takes %d channels, so trimap must be %s" %
                              (type(model).__name__, model.IN_CH, model.IN_CH == 7))
-        if static_bg is not None:
-            static_bg = np.asarray(static_bg)
-            if static_bg.dtype != np.uint8:
-                raise TypeError("FrameStream: static_bg must be uint8, got %s" % static_bg.dtype)
-            if static_bg.shape != (h, w, 3):
-                raise ValueError("FrameStream: static_bg must be [h,w,3] = %s, got %s" % ((h, w, 3), static_bg.shape))
-            static_bg = np.ascontiguousarray(static_bg)
+        static_bg = check_static_bg("FrameStream", static_bg, h, w)
         self.model, self.h, self.w, self.chunk, self.depth = model, h, w, chunk, depth
         self.trimap, self.static_bg, self.out, self.graph = bool(trimap), static_bg, out, bool(graph)
         self.device = model.device
-        self.native = not model.x6mode and model.dtype == torch.bfloat16  # bf16 8-channel frames, else f32
         self.overflowed_chunks = []
-        self._slots = None   # built with the first valid item: nothing touches the device before that
         self._plate = None
         self._x6 = None
-        self._upload = self._compute = None
 
     # ------------------------------------------------------------------ checks (host only)
     def check_item(self, item):
@@ -123,53 +97,35 @@ class FrameStream:
 
     # ------------------------------------------------------------------ device side
     def _setup(self):
-        dev = self.device
         self.model.prepare()
-        self._upload, self._compute = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+        self._make_streams()
         if self.static_bg is not None:
-            self._plate = torch.from_numpy(self.static_bg).to(dev)
+            self._plate = torch.from_numpy(self.static_bg).to(self.device)
         self._slots = [_Slot(self) for _ in range(self.depth)]
-        torch.cuda.synchronize(dev)  # the plate and the zeroed pad channels, before another stream reads them
+        torch.cuda.synchronize(self.device)  # the plate and the zeroed pad channels, before another stream reads them
 
     def _chain(self, s, k):
         """Ingest -> forward -> quantise -> download of the slot's first k frames, on the current stream."""
         bg = self._plate if self._plate is not None else s.d_bg[:k]
         ops.frames_from_u8(s.d_cmp[:k], bg, None if s.d_tri is None else s.d_tri[:k], out=s.frames[:k])
         self.model.forward(s.frames[:k], out=s.alpha[:k], overflow=s.flag)
-        self._finish(s, k)
-
-    def _finish(self, s, k):
-        if s.q is None:
-            s.h_out[:k].copy_(s.alpha[:k, :, :, 0], non_blocking=True)
-        else:
-            ops.matte_quantize(s.alpha[:k], out=s.q[:k], bits=OUT_DTYPES[self.out][2])
-            s.h_out[:k].copy_(s.q[:k], non_blocking=True)
-        if s.flag is not None:
-            s.h_flag.copy_(s.flag, non_blocking=True)
+        s.download(s.alpha[:k])
 
     def _capture(self, s):
         """The full-chunk chain of one slot as one HIP graph: UNet.capture records the forward over the slot's static
         buffers with the ingest before it and the quantisation and download after it, all on the capturing stream."""
-        n = self.chunk
         bg = self._plate if self._plate is not None else s.d_bg
         s.graph = self.model.capture(
             s.frames, static=True, out=s.alpha, overflow=s.flag,
             pre=lambda: ops.frames_from_u8(s.d_cmp, bg, s.d_tri, out=s.frames),
-            post=lambda: self._finish(s, n))
+            post=lambda: s.download(s.alpha))
 
     def _submit(self, s, index, cmp, bg, tri, k):
         s.k, s.index = k, index
-        s.h_cmp[:k].numpy()[...] = cmp
-        if bg is not None:
-            s.h_bg[:k].numpy()[...] = bg
-        if tri is not None:
-            s.h_tri[:k].numpy()[...] = tri
+        for name, a in (("cmp", cmp), ("bg", bg), ("tri", tri)):
+            s.stage(name, a, k)
         with torch.cuda.stream(self._upload):
-            s.d_cmp[:k].copy_(s.h_cmp[:k], non_blocking=True)
-            if bg is not None:
-                s.d_bg[:k].copy_(s.h_bg[:k], non_blocking=True)
-            if tri is not None:
-                s.d_tri[:k].copy_(s.h_tri[:k], non_blocking=True)
+            s.upload(k)
             s.uploaded.record(self._upload)
         with torch.cuda.stream(self._compute):
             self._compute.wait_event(s.uploaded)
@@ -187,47 +143,14 @@ class FrameStream:
         if s.h_flag is not None and int(s.h_flag[0]):
             # the chunk left fp16's range: the same frames on bf16x6 (f32 range), re-quantised and re-downloaded
             self.overflowed_chunks.append(s.index)
-            if self._x6 is None:
-                from .split6 import Split6Forward
-                self._x6 = Split6Forward(self.model)  # reads the model's parameters only
             with torch.cuda.stream(self._compute):
-                self._x6.forward(s.frames[:k], out=s.alpha[:k])
+                rerun_x6(self, s.frames[:k], s.alpha[:k])
                 s.flag.zero_()
-                self._finish(s, k)
+                s.download(s.alpha[:k])
             self._compute.synchronize()
         return s.h_out[:k].numpy().copy()
 
     def run(self, source):
         """Generator: one [k,h,w] matte (numpy, the ``out`` dtype) per source item, in source order."""
         self.overflowed_chunks = []
-        inflight, error, index = [], None, 0
-        it = iter(source)
-        try:
-            while True:
-                try:
-                    item = next(it)
-                    cmp, bg, tri, k = self.check_item(item)
-                except StopIteration:
-                    break
-                except Exception as e:  # the source failed or yielded a bad item: finish what was taken, then raise
-                    error = e
-                    break
-                if self._slots is None:
-                    self._setup()
-                if index == 0:  # what the caller queued (e.g. on the model's buffers) comes first
-                    self._compute.wait_stream(torch.cuda.current_stream(self.device))
-                s = self._slots[index % self.depth]
-                self._submit(s, index, cmp, bg, tri, k)
-                index += 1
-                inflight.append(s)
-                if len(inflight) >= self.depth:
-                    yield self._retire(inflight.pop(0))
-            while inflight:
-                yield self._retire(inflight.pop(0))
-        finally:
-            # also when the consumer abandons the generator: nothing stays queued on the slots
-            if self._slots is not None:
-                self._upload.synchronize()
-                self._compute.synchronize()
-        if error is not None:
-            raise error
+        yield from super().run(source)

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import ops, parallel
+from .graphs import capture_passes
 from .layers import EPS
 from .unet_simple import CIN_PAD, NEW_CONVS, UNetSimple, Vgg16, _levels
 
@@ -65,10 +66,37 @@ def param_layout():
     return out, off
 
 
+def _to_device_f32(t, device):
+    """A numpy array or a tensor as a contiguous f32 tensor on ``device`` (itself when it already is one)."""
+    if not isinstance(t, torch.Tensor):
+        t = torch.from_numpy(np.ascontiguousarray(t, np.float32))
+    return t.to(device, torch.float32).contiguous()
+
+
 class TrainerBase:
-    """What the training steps of train.py (video_procedure / simple_procedure) and small_train.py
-    (small_training) share: the flat f32 parameter / gradient / Adam-slot buffers, batch statistics with optional
-    SyncBN, the BN backward, the DDP exchange and tf.train.AdamOptimizer's update."""
+    """What the training steps of train.py (video_procedure / simple_procedure), training_procedure
+    (image_train.py) and small_train.py (small_training) share: the flat f32 parameter / gradient / Adam-slot
+    buffers, batch statistics with optional SyncBN, the BN backward, the DDP exchange, tf.train.AdamOptimizer's
+    update and the step itself.  A trainer supplies forward(*inputs), which leaves the predicted matte in ``output``,
+    backward(gt, raw_fg, bg, cmp), _refresh_packs() and _bufs(): its lazily built buffer dict (valid after a forward),
+    whose "loss" entry takes the step's [3] losses.  A batch is (cmp, bg, [further inputs,] gt, raw_fg)."""
+
+    def _graph_tensors(self):
+        """The buffers a capture's warm-up allocates (graphs.capture_passes)."""
+        return self._bufs().values()
+
+    def step(self, *batch):
+        """One training iteration on a batch (cmp, bg, [warped,] gt, raw_fg); returns a new device tensor [loss,
+        alpha_loss, compositional_loss] (pre-update), not aliased to the trainer's buffers."""
+        batch = [_to_device_f32(t, self.device) for t in batch]
+        self.forward(*batch[:-2])
+        gt, raw_fg, bg, cmp = batch[-2], batch[-1], batch[1], batch[0]
+        loss = self._bufs()["loss"]
+        loss.copy_(ops.matting_loss(self.output, gt, raw_fg, bg, cmp))
+        self.grad.zero_()
+        self.backward(gt, raw_fg, bg, cmp)
+        self.apply_gradients()
+        return loss.clone()
 
     def _init_flat(self, layout, n, lr, beta1, beta2, epsilon, sync_bn):
         self.lr, self.beta1, self.beta2, self.epsilon = lr, beta1, beta2, epsilon
@@ -140,6 +168,45 @@ class TrainerBase:
         lr_t = np.float32(np.float32(self.lr) * np.sqrt(one - self._b2p) / (one - self._b1p))
         ops.adam_tf(self.flat, self.m, self.v, self.grad, lr_t, self.beta1, self.beta2, self.epsilon, scale)
         self._refresh_packs()
+
+
+class TrainGraphBase:
+    """A trainer's capture() result: one step's forward + loss and its backward as two HIP graphs (``g_fwd``,
+    ``g_bwd``) over ``inputs``, the static batch buffers they read.  ``step(*batch)`` = the trainer's step on graph
+    replays; the DDP exchange + Adam + re-pack stay eager.  The trainer's ``_graph_tensors()`` names the buffers
+    the warm-up allocates (graphs.capture_passes)."""
+
+    def __init__(self, trn, *batch):
+        self.trn = trn
+        self.inputs = [_to_device_f32(t, trn.device).clone() for t in batch]
+        self.g_fwd, self.g_bwd = self._capture()
+
+    def _capture(self, hook=None):
+        trn = self.trn
+        return capture_passes(trn.device, [self._forward, self._backward], trn._graph_tensors, hook)[0]
+
+    def _forward(self):
+        b, t = self.inputs, self.trn
+        t.forward(*b[:-2])
+        t._bufs()["loss"].copy_(ops.matting_loss(t.output, b[-2], b[-1], b[1], b[0]))
+
+    def _backward(self):
+        b = self.inputs
+        self.trn.grad.zero_()
+        self.trn.backward(b[-2], b[-1], b[1], b[0])
+
+    def load(self, *batch):
+        for dst, src in zip(self.inputs, batch):
+            dst.copy_(src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src, np.float32)))
+
+    def step(self, *batch):
+        """One training iteration on graph replays; returns [loss, alpha_loss, compositional_loss] (pre-update)."""
+        if batch:
+            self.load(*batch)
+        self.g_fwd.replay()
+        self.g_bwd.replay()
+        self.trn.apply_gradients()
+        return self.trn._bufs()["loss"].clone()
 
 
 class VideoTrainer(TrainerBase):
@@ -318,9 +385,7 @@ class VideoTrainer(TrainerBase):
     def forward(self, cmp, bg, warped):
         self._check_capture_fork()
         m = self.model
-        xs = [t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t, np.float32))
-              for t in (cmp, bg, warped)]
-        xs = [t.to(self.device, torch.float32) for t in xs]
+        xs = [_to_device_f32(t, self.device) for t in (cmp, bg, warped)]
         n, h, w, _ = xs[0].shape
         b = m._buffers(n, h, w)
         tb = self._train_buffers(n, h, w)
@@ -488,20 +553,8 @@ class VideoTrainer(TrainerBase):
             torch._foreach_copy_([bp[:cout] for _, bp, cout in self._padconv.values()],
                                  [self.P[scope, "b"] for scope in self._padconv])
 
-    def step(self, cmp, bg, warped, gt, raw_fg):
-        """One training iteration; returns a new device tensor [loss, alpha_loss, compositional_loss] (pre-update),
-        not aliased to the trainer's buffers."""
-        self.forward(cmp, bg, warped)
-        dev = lambda t: (t if isinstance(t, torch.Tensor) else torch.from_numpy(  # noqa: E731
-            np.ascontiguousarray(t, np.float32))).to(self.device, torch.float32).contiguous()
-        gt, raw_fg, bg_d, cmp_d = dev(gt), dev(raw_fg), dev(bg), dev(cmp)
-        tb = self._tb
-        loss = ops.matting_loss(tb["alpha"], gt, raw_fg, bg_d, cmp_d)
-        tb["loss"].copy_(loss)
-        self.grad.zero_()
-        self.backward(gt, raw_fg, bg_d, cmp_d)
-        self.apply_gradients()
-        return tb["loss"].clone()
+    def _bufs(self):
+        return self._tb
 
     def capture(self, cmp, bg, warped, gt, raw_fg):
         """Record one step's forward + loss and its backward over batches shaped like these as two HIP graphs
@@ -519,7 +572,7 @@ class VideoTrainer(TrainerBase):
         return conv, bn
 
 
-class TrainGraph:
+class TrainGraph(TrainGraphBase):
     """VideoTrainer.capture's result: ``step(cmp, bg, warped, gt, raw_fg)`` = VideoTrainer.step on graph replays;
     ``inputs`` are the static batch buffers the graphs read."""
 
@@ -527,53 +580,14 @@ class TrainGraph:
         if trn.sync_bn and torch.distributed.get_backend() != "nccl":
             raise NotImplementedError("capture with sync_bn needs the nccl (RCCL) backend: gloo collectives are not "
                                       "graph-capturable")
-        dev = trn.device
-        self.trn = trn
-        self.inputs = [(t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t, np.float32)))
-                       .to(dev, torch.float32).contiguous().clone() for t in batch]
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):  # lazily built buffers / workspaces, no parameter update
-            self._forward()
-            self._backward()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        for t in trn._tb.values():  # allocated on the side stream, replayed on the caller's
-            for u in (t if isinstance(t, tuple) else (t,)):
-                if isinstance(u, torch.Tensor):
-                    u.record_stream(torch.cuda.current_stream(dev))
-        self.g_fwd, self.g_bwd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        super().__init__(trn, *batch)
+
+    def _capture(self):
+        trn = self.trn
+
+        def origin():  # the stream each pass's capture began on (see _check_capture_fork)
+            trn._capture_origin = torch.cuda.current_stream(trn.device)
         try:
-            with torch.cuda.graph(self.g_fwd):
-                trn._capture_origin = torch.cuda.current_stream(dev)
-                self._forward()
-            with torch.cuda.graph(self.g_bwd):
-                trn._capture_origin = torch.cuda.current_stream(dev)
-                self._backward()
+            return super()._capture(origin)
         finally:
             trn._capture_origin = None
-
-    def _forward(self):
-        cmp, bg, warped, gt, fg = self.inputs
-        t = self.trn
-        t.forward(cmp, bg, warped)
-        t._tb["loss"].copy_(ops.matting_loss(t._tb["alpha"], gt, fg, bg, cmp))
-
-    def _backward(self):
-        cmp, bg, warped, gt, fg = self.inputs
-        self.trn.grad.zero_()
-        self.trn.backward(gt, fg, bg, cmp)
-
-    def load(self, *batch):
-        for dst, src in zip(self.inputs, batch):
-            dst.copy_(src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src, np.float32)))
-
-    def step(self, *batch):
-        """One training iteration on graph replays; returns [loss, alpha_loss, compositional_loss] (pre-update)."""
-        if batch:
-            self.load(*batch)
-        self.g_fwd.replay()
-        self.g_bwd.replay()
-        self.trn.apply_gradients()
-        return self.trn._tb["loss"].clone()
-

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .graphs import capture_passes, chained
 from .weights import init_conv, load_vgg16
 
 # fresh convs in graph-build order (unet.py:191-203): scope, cin, cout, keeps bias
@@ -446,35 +447,12 @@ class GraphedForward:
         self.overflow = overflow  # (kept alive with the graph that writes it)
         if static:
             self.input = x
-        elif x.dtype == torch.bfloat16:  # a frame in the compute dtype: its own 8-channel buffer, pad zero
-            self.input = torch.zeros(tuple(x.shape[:3]) + (8,), dtype=x.dtype, device=x.device)[..., :x.shape[3]]
+        else:  # a frame in the compute dtype gets its own 8-channel buffer, an f32 one an f32 buffer
+            self.input = ops.frame_buffer(model, *x.shape[:3], native=x.dtype == torch.bfloat16)
             self.input.copy_(x)
-        else:
-            self.input = torch.empty_like(x)
-            self.input.copy_(x)
-
-        def run():
-            if pre is not None:
-                pre()
-            o = model.forward(self.input, out, overflow)
-            if post is not None:
-                post()
-            return o
-        side = torch.cuda.Stream(device=self.input.device)
-        side.wait_stream(torch.cuda.current_stream(self.input.device))
-        with torch.cuda.stream(side):  # lazily built kernels/weights (folded filters, attributes) before capture
-            run()
-        main =torch.cuda.current_stream(self.input.device)
-        main.wait_stream(side)
-        torch.cuda.synchronize(self.input.device)
-        # the buffer set (and any lazily allocated entry) was allocated on the side stream but the graph replays on
-        # the caller's: tell the caching allocator, so a set freed later (the model moved to another shape and this
-        # graph was dropped) is not handed out again while replays queued on that stream may still use it
-        for t in model._ws.values():
-            t.record_stream(main)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.output = run()
+        run = chained(pre, lambda: model.forward(self.input, out, overflow), post)
+        # the model's buffer set (and any lazily allocated entry of it) is what the warm-up allocates
+        (self.graph,), (self.output,) = capture_passes(self.input.device, [run], lambda: model._ws.values())
         # the buffer set the graph writes stays alive with the graph; so does the forward's host-side state
         self._ws, self._ws_key = model._ws, model._ws_key
         self._skip_valid = model._skip_valid

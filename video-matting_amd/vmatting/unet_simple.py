@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .graphs import capture_passes, chained
 from .layers import BatchNorm, conv_bn
 from .weights import init_conv, load_vgg16
 
@@ -298,27 +299,11 @@ class GraphedFed:
 
     def __init__(self, model, n, h, w, towers=(0, 1, 2), pre=None, post=None):
         self.model = model
-        dev = model.device
-
-        def run():
-            if pre is not None:
-                pre()
-            o = model.forward_fed(n, h, w, towers)
-            if post is not None:
-                post()
-            return o
-        b = model._buffers(n, h, w)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):  # lazily built workspaces and kernel attributes, before the capture
-            run()
-        main = torch.cuda.current_stream(dev)
-        main.wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.output = run()
-        self._ws = b  # the buffers the graph reads and writes stay alive with it
+        run = chained(pre, lambda: model.forward_fed(n, h, w, towers), post)
+        self._ws = model._buffers(n, h, w)  # the buffers the graph reads and writes stay alive with it
+        (self.graph,), (self.output,) = capture_passes(
+            model.device, [run],
+            lambda: [t.base if isinstance(t, ops.SourceConcat) else t for t in self._ws.values()])
 
     def replay(self):
         self.graph.replay()

@@ -14,6 +14,7 @@ activation buffers (they run in order on one stream).
 import torch
 
 from . import ops, parallel
+from .split6 import rerun_x6
 
 VGG_MEAN = (103.939, 116.779, 123.68)  # params.py:10
 
@@ -91,11 +92,7 @@ class VideoMatter:
             ops._require_gpu(t)
             if not t.is_contiguous():
                 raise ValueError("from_uint8: contiguous uint8 tensors expected")
-        if not model.x6mode and model.dtype == torch.bfloat16:
-            frames = torch.zeros((f, h, w, 8), dtype=torch.bfloat16, device=cmp.device)[..., :c]
-        else:
-            frames = torch.empty((f, h, w, c), dtype=torch.float32, device=cmp.device)
-        return cls(model, frames, chunk, graph, alpha, _u8=(cmp, bg, trimap))
+        return cls(model, ops.frame_buffer(model, f, h, w), chunk, graph, alpha, _u8=(cmp, bg, trimap))
 
     def _ingest(self, k):
         a, b = self.spans[k]
@@ -122,12 +119,9 @@ class VideoMatter:
                 self.model.forward(self.frames[a:b], out=self.alpha[a:b], overflow=self._slot(k))
         if self._slots is not None:
             self.overflowed_chunks = [k for k, v in enumerate(self._slots.tolist()) if v]
-            if self.overflowed_chunks and self._x6 is None:
-                from .split6 import Split6Forward
-                self._x6 = Split6Forward(self.model)  # reads the model's parameters only
             for k in self.overflowed_chunks:
                 a, b = self.spans[k]
-                self._x6.forward(self.frames[a:b], out=self.alpha[a:b])
+                rerun_x6(self, self.frames[a:b], self.alpha[a:b])
         return self.alpha
 
 
