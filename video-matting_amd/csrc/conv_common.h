@@ -1,5 +1,5 @@
-// Conv argument block and device helpers shared by the 3x3 conv kernels (conv3x3.hip, conv_rows.hip, conv_pair.hip)
-// and train.hip's MFMA kernels.  Device code only: the host side (options, launchers) is conv_dispatch.h.
+// Conv argument block and device helpers shared by the 3x3 conv kernels (conv3x3.hip, conv_rows.hip, conv_pair.hip,
+// conv_first.hip, conv_head.hip) and train.hip's MFMA kernels.  Device code only: the host side (options, launchers) is conv_dispatch.h.
 #pragma once
 
 #include <type_traits>
@@ -241,6 +241,6 @@ __device__ __forceinline__ uint4 chunk_pair(uint2 lo, uint2 hi) {
   return make_uint4(sx[0], sy[0], sx[1], sy[1]);
 }
 
-// (the options, the launchers of conv_rows.hip / conv_pair.hip and g_last_kernel: conv_dispatch.h)
+// (the options, the launchers of the other conv files and g_last_kernel: conv_dispatch.h)
 
 }  // namespace vm

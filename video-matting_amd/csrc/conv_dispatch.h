@@ -1,5 +1,6 @@
-// Host side of the 3x3 conv translation units (conv3x3.hip, conv_rows.hip, conv_pair.hip): the tuning options
-// (vm_set_option) and the launchers through which conv3x3.hip's routing reaches the kernels of the other files.
+// Host side of the 3x3 conv translation units (conv3x3.hip, conv_rows.hip, conv_pair.hip, conv_first.hip,
+// conv_head.hip): the tuning options (vm_set_option), the call and filter-geometry structs, and the launchers through
+// which conv3x3.hip's routing reaches the kernels of the other files.
 #pragma once
 
 #include "conv_common.h"
@@ -91,11 +92,71 @@ extern ConvOptions g_opt;
 // (bench.py matches its per-launch PMC traffic by this name); defined in conv3x3.hip
 extern thread_local char g_last_kernel[128];
 
+// geometry of a packed filter (vm_conv3x3_pack_weights; the K layout of conv3x3.hip's header comment)
+struct PackGeom {
+  int cin_pad, ge, K9, K_pad, cout_pad, chunk_major, ng;
+};
+
+inline PackGeom geom(int cin, int cout, int dtype) {
+  PackGeom g;
+  g.ge = 64 / elem_bytes(dtype);
+  g.cin_pad = (cin + 7) / 8 * 8;
+  g.K9 = 9 * g.cin_pad;
+  g.chunk_major = g.cin_pad % g.ge == 0;
+  g.ng = g.chunk_major ? g.K9 / g.ge : 0;
+  g.K_pad = (g.K9 + 2 * g.ge - 1) / (2 * g.ge) * (2 * g.ge);  // whole 128-byte steps
+  g.cout_pad = (cout + 63) / 64 * 64;
+  return g;
+}
+
+inline void fill_geom(ConvArgs& a, const PackGeom& g) {
+  a.cin_pad = g.cin_pad;
+  a.K9 = g.K9;
+  a.chunk_major = g.chunk_major;
+  a.ng = g.ng;
+  a.K_pad = g.K_pad;
+  a.cout_pad = g.cout_pad;
+}
+
+// split-fp16 x3 output of vm_conv3x3_split3_nhwc (ConvArgs::ysplit / psplit / ovf)
+struct SplitOut {
+  int yslab, pslab;
+  int* ovf;
+};
+
+// One conv call as the C entry points hand it to conv_impl: the arguments every entry point has, then the optional ones
+struct ConvCall {
+  const vm_tensor* x;
+  const void* packed;
+  int cin, cout;
+  const float* bias;
+  const float* scale;
+  const float* shift;
+  int act;
+  vm_tensor* y;
+  void* stream;
+  const vm_tensor* yp = nullptr;  // fused 2x2/2 SAME max-pool output
+  float* y2 = nullptr;            // cout == 1: sigmoid of the pre-activation value (HeadArgs::y2)
+  int nsrc = 0;                   // > 1: split sources, x the view of source 0, source s at s * src_stride elements
+  long src_stride = 0;
+  void* work = nullptr;           // split-K workspace (vm_conv3x3_workspace_bytes)
+  size_t work_bytes = 0;
+  const float* head_part = nullptr;  // cout == 1: HeadArgs::part
+  const float* y_acc = nullptr;      // cout == 1: HeadArgs::yacc
+  const SplitOut* so = nullptr;      // split-fp16 x3 output
+};
+
 // launchers defined in conv_rows.hip (called from conv3x3.hip's dispatch)
 bool rows_ok(const ConvArgs& a);
 int launch_rows(ConvArgs& a, hipStream_t st, int cfg);
 // launchers defined in conv_pair.hip
 bool pair_strip_ok(const ConvArgs& a);
 int launch_pair_strip(ConvArgs& a, long nimg, hipStream_t st);
+// launchers defined in conv_first.hip (dispatch_mfma decides when they apply)
+int launch_first(ConvArgs& a, hipStream_t st);
+int launch_first_softmax(ConvArgs& a, hipStream_t st);
+int launch_first_softmax_f32(ConvArgs& a, int cin, hipStream_t st);
+// conv_head.hip: conv_impl's cout == 1 route (tile choice, head_th, head_kernel)
+int dispatch_head(const ConvCall& c, const PackGeom& g, int xalias, long M, hipStream_t st);
 
 }  // namespace vm
