@@ -616,6 +616,28 @@ int vm_frames_from_u8(const uint8_t* cmp, const uint8_t* bg, const uint8_t* trim
  * 65535.f (bits 16, uint16 out); f32 product, ties to even, NaN -> 0. */
 int vm_matte_quantize(const float* alpha, long pixels, int bits, void* out, void* stream);
 
+/* The matte applied.  The composite is C = a F + (1 - a) B and the background B is known (it is a model input), so
+ * the foreground layer and the frame over another plate N, C + (1 - a)(N - B), follow per pixel.
+ *   alpha f32 [n,h,w]; cmp uint8 [n,h,w,3] BGR; bg uint8 [nb,h,w,3], nb == n or 1 (one static plate)
+ *   mode VM_COMPOSE_OVER: out uint8 [n,h,w,3] BGR, new_bg uint8 [nn,h,w,3] required, nn == n or 1
+ *   mode VM_COMPOSE_STRAIGHT, VM_COMPOSE_PREMUL: out uint8 [n,h,w,4] BGRA, new_bg NULL and nn 0
+ * Arithmetic, all float64, nothing contracted, one rounding at the end: fin(v) = (uint8) rint(min(max(v, 0), 255)),
+ * ties to even; q = the 8-bit matte of vm_matte_quantize; c, b, nw the bytes of cmp, bg, new_bg, per BGR channel:
+ *   OVER      a = (double)alpha clamped to [0,1], NaN -> 0;  out = fin(c + (1 - a) * (nw - b))
+ *   PREMUL    out = fin(c - ((255 - q) * b) / 255), A = q: the layer a F with a = q / 255, the stored alpha
+ *   STRAIGHT  q == 0: B = G = R = 0; else out = fin(b + ((c - b) * 255) / q), A = q (the reference's foreground
+ *             files: data.create_bgra, reader.read_fg_img)
+ * (255 - q) b and (c - b) 255 are exact, so each layer value has one rounding division.  Traffic per pixel: 4 B alpha
+ * + 3 B cmp + 3 B bg read (a static plate is re-read from cache), + 3 B new plate for OVER, 3 or 4 B written: 13 - 16
+ * B, HBM-bound.  4 pixels per thread (one 16-byte alpha load, 3 dwords per uint8 plane, one 16-byte BGRA or three
+ * dword BGR stores) when alpha is 16-byte, the uint8 planes 4-byte, a BGRA out 16-byte and a BGR out 4-byte aligned;
+ * else one pixel per thread.  No TF counterpart (the reference composites forward only, reader.py:72-79). */
+#define VM_COMPOSE_OVER 0
+#define VM_COMPOSE_STRAIGHT 1
+#define VM_COMPOSE_PREMUL 2
+int vm_matte_compose(const float* alpha, const uint8_t* cmp, const uint8_t* bg, int nb, const uint8_t* new_bg, int nn,
+                     int n, int h, int w, int mode, uint8_t* out, void* stream);
+
 /* The video model's feed in one pass: everything UNetSimple reads for the recurrence of train.py:346-366 at inference,
  *   alpha[t] = create_model(cmp[t], bg[t], warp_img(alpha[t-1], backward[t]), phase False)   (unet_simple.py:148-152),
  * from a decoded clip.  n, h, w are read from `cat`.

@@ -1,8 +1,11 @@
 """Measure the video model's clip path: the fused feed kernel beside the unfused route it replaces, the per-frame graph
 and its parts, the host link, and ClipStream from host arrays.  Prints one JSON line and writes it to
-profiles/clip_stream.json.
+profiles/clip_stream.json.  The compose section (``--sections compose``) runs ClipStream with out="over" (a static
+new plate) beside out="u8" on the same clip, their runs interleaved in one process; it prints a second JSON line and
+writes it under "clip_bench" in profiles/compose_stream.json.
 
     python tools/clip_bench.py [--sizes 500x1200,1080x1920] [--frames 48] [--reps 9] [--dtype bf16]
+                               [--sections clip,compose]
 
 Kernel times are hipEvent medians over ``--reps`` runs after a warm-up; every run of a kernel works on another of
 several buffer sets, so its inputs and outputs do not sit in the 256 MB memory-side cache between runs.  The fused and
@@ -261,6 +264,55 @@ def measure(h, w, a, vgg, params):
     return res
 
 
+def measure_compose(h, w, a, vgg, params):
+    """ClipStream frames/s with out="u8" and out="over" (static original and new plates, the plate's tower reused),
+    interleaved: every round runs each output once."""
+    from oracle.flow import smooth_flow
+    from vmatting import ClipStream, unet_simple
+    np.random.seed(0)
+    model = unet_simple.UNetSimple(unet_simple.Vgg16(vgg, a.dtype), False, a.dtype).load_params(params)
+    rs = np.random.RandomState(1)
+    F = a.frames
+    cmp, bg = (rs.randint(0, 256, (2, h, w, 3), dtype=np.uint8) for _ in range(2))
+    plate = rs.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    alpha0 = rs.uniform(size=(h, w)).astype(np.float32)
+    bwn = smooth_flow(h, w, seed=7, amp=6.0)
+
+    def source():
+        for i in range(F):
+            yield cmp[i % 2], None, bwn, None
+    kw = dict(depth=2, static_bg=bg[0], reuse_bg_tower=True, thresh=a.thresh)
+    streams = {"u8": ClipStream(model, h, w, out="u8", **kw), "over": ClipStream(model, h, w, out="over", new_bg=plate, **kw)}
+
+    def run(cs):
+        t0 = time.perf_counter()
+        tot = sum(1 for _ in cs.run(source(), alpha0))
+        torch.cuda.synchronize()
+        assert tot == F
+        return (time.perf_counter() - t0) * 1e3
+
+    def streamed():
+        times = {name: [] for name in streams}
+        for i in range(1 + max(3, a.reps // 3)):  # round 0 warms up (and captures the graphs)
+            for name, cs in streams.items():
+                ms = run(cs)
+                if i:
+                    times[name].append(ms)
+        out = {}
+        for name, t in times.items():
+            ms = statistics.median(t)
+            out["clip_stream_plate_reuse_" + name] = {"ms_per_frame": round(ms / F, 3), "frames_per_s": round(F / ms * 1e3, 1),
+                                                      "min_ms_per_frame": round(min(t) / F, 3),
+                                                      "max_ms_per_frame": round(max(t) / F, 3)}
+        out["over_keeps_of_u8"] = round(out["clip_stream_plate_reuse_over"]["frames_per_s"] /
+                                        out["clip_stream_plate_reuse_u8"]["frames_per_s"], 3)
+        return out
+    res = step("compose streamed %dx%d" % (h, w), a.step_limit, streamed)
+    del streams, model
+    torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="500x1200,1080x1920")
@@ -271,23 +323,40 @@ def main():
     ap.add_argument("--sets", type=int, default=5, help="buffer sets the kernel timings cycle through")
     ap.add_argument("--step-limit", type=int, default=150)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "clip_stream.json"))
+    ap.add_argument("--compose-out", default=os.path.join(REPO, "profiles", "compose_stream.json"))
+    ap.add_argument("--sections", default="clip,compose", help="comma-separated: clip, compose")
     a = ap.parse_args()
+    sections = set(a.sections.split(","))
+    if not sections or sections - {"clip", "compose"}:
+        raise SystemExit("clip_bench: --sections takes clip and / or compose, got %r" % a.sections)
     if not torch.cuda.is_available():
         raise SystemExit("clip_bench needs a ROCm GPU")
     from oracle import models as om
     from vmatting.weights import synthetic_vgg16
     vgg = synthetic_vgg16(0)
     params = om.unet_simple_params(np.random.RandomState(1))
-    res = {"device": torch.cuda.get_device_name(0), "dtype": a.dtype, "frames": a.frames, "reps": a.reps,
-           "hbm_peak_GBps": HBM_PEAK / 1e9, "sizes": {}}
-    for size in a.sizes.split(","):
-        h, w = (int(v) for v in size.split("x"))
-        res["sizes"][size] = measure(h, w, a, vgg, params)
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    head = {"device": torch.cuda.get_device_name(0), "dtype": a.dtype, "frames": a.frames, "reps": a.reps}
+    sizes = [tuple(int(v) for v in size.split("x")) for size in a.sizes.split(",")]
+    if "clip" in sections:
+        res = dict(head, hbm_peak_GBps=HBM_PEAK / 1e9, sizes={})
+        for h, w in sizes:
+            res["sizes"]["%dx%d" % (h, w)] = measure(h, w, a, vgg, params)
+        line = json.dumps(res)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+        print(line)
+    if "compose" in sections:
+        res = dict(head, sizes={"%dx%d" % (h, w): measure_compose(h, w, a, vgg, params) for h, w in sizes})
+        doc = {}
+        if os.path.exists(a.compose_out):
+            with open(a.compose_out) as f:
+                doc = json.load(f)
+        doc["clip_bench"] = res
+        os.makedirs(os.path.dirname(a.compose_out), exist_ok=True)
+        with open(a.compose_out, "w") as f:
+            f.write(json.dumps(doc) + "\n")
+        print(json.dumps(res))
 
 
 if __name__ == "__main__":

@@ -1,8 +1,12 @@
 """Measure the clip ends: the ingest and quantise kernels, the torch route they replace, the host link, and the
 streamed pipeline beside the resident-frames VideoMatter.  Prints one JSON line and writes it to
-profiles/ingest_stream.json.
+profiles/ingest_stream.json.  The compose section (``--sections compose``) measures vm_matte_compose the same way: the
+three modes with per-frame and static plates, the torch route to the same bytes (float64 elementwise ops, bit-equal
+output asserted), and FrameStream with out="u8" / "over" / "bgra" interleaved in one process; it prints a second JSON
+line and writes it under "stream_bench" in profiles/compose_stream.json.
 
     python tools/stream_bench.py [--frames 64] [--chunk 8] [--height 1080] [--width 1920] [--reps 9]
+                                 [--sections ingest,compose]
 
 Kernel times are hipEvent medians over ``--reps`` runs after a warm-up; every run of a kernel works on another of
 several buffer sets, so the 83 MB alpha of the quantise kernel does not sit in the 256 MB memory-side cache between
@@ -72,6 +76,140 @@ def rate(nbytes, ms):
     return {"ms": round(ms, 4), "GBps": round(nbytes / ms / 1e6, 1), "hbm_frac": round(nbytes / (ms * 1e-3) / HBM_PEAK, 3)}
 
 
+def merge_json(path, key, value):
+    """Write ``value`` under ``key`` of the JSON object in ``path``, keeping what other tools wrote there."""
+    doc = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            doc = json.load(f)
+    doc[key] = value
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(json.dumps(doc) + "\n")
+
+
+def compose_bytes(px, hw, mode, static_bg, static_nw):
+    """Algorithmic bytes of one vm_matte_compose call: alpha + cmp + bg (+ new plate) read once, the result written
+    once; a static plate counts once, not per frame."""
+    plate = lambda static: hw * 3 if static else px * 3  # noqa: E731
+    return px * (4 + 3) + plate(static_bg) + (plate(static_nw) if mode == "over" else 0) + px * (3 if mode == "over" else 4)
+
+
+def torch_compose(alpha, cmp, bg, new_bg, mode):
+    """The same bytes by torch ops on the device: float64 elementwise, one rounding (half to even)."""
+    c, b = cmp.double(), bg.double()
+    fin = lambda v: v.clamp(0.0, 255.0).round().to(torch.uint8)  # noqa: E731
+    if mode == "over":
+        a = alpha.double().clamp(0.0, 1.0)
+        return fin(c + (1.0 - a) * (new_bg.double() - b))
+    q = (alpha * 255.0).round().clamp(0.0, 255.0)
+    qd = q.double()
+    if mode == "premul":
+        bgr = fin(c - ((255.0 - qd) * b) / 255.0)
+    else:
+        bgr = torch.where(qd == 0.0, torch.zeros((), dtype=torch.uint8, device=cmp.device),
+                          fin(b + ((c - b) * 255.0) / qd.clamp(min=1.0)))
+    return torch.cat([bgr, q.to(torch.uint8)], -1)
+
+
+def compose_section(a):
+    """vm_matte_compose at [chunk, height, width]: kernel times, the torch route, FrameStream with the new outputs."""
+    from vmatting import FrameStream, ops, unet
+    from vmatting.weights import synthetic_vgg16
+    n, h, w, F = a.chunk, a.height, a.width, a.frames
+    px, hw = n * h * w, h * w
+    res = {"shape": [n, h, w], "frames": F, "reps": a.reps, "device": torch.cuda.get_device_name(0),
+           "hbm_peak_GBps": HBM_PEAK / 1e9}
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0)
+    u8 = lambda: torch.randint(0, 256, (n, h, w, 3), generator=g, device="cuda", dtype=torch.uint8)  # noqa: E731
+    # one set is 4 + 3 + 3 + 3 + 4 B per pixel = 282 MB at 8 x 1080 x 1920: past the 256 MB memory-side cache
+    sets = [dict(alpha=torch.rand((n, h, w, 1), generator=g, device="cuda"), cmp=u8(), bg=u8(), nw=u8())
+            for _ in range(a.sets)]
+
+    def kernels():
+        out = {}
+        for mode in ("over", "bgra", "premul"):
+            o = [torch.empty((n, h, w, 3 if mode == "over" else 4), dtype=torch.uint8, device="cuda") for _ in sets]
+            plates = [(False, False), (True, False)] + ([(False, True), (True, True)] if mode == "over" else [])
+            for static_bg, static_nw in plates:
+                def call(s, dst):
+                    bg = s["bg"][0] if static_bg else s["bg"]
+                    nw = None if mode != "over" else s["nw"][0] if static_nw else s["nw"]
+                    return ops.matte_compose(s["alpha"], s["cmp"], bg, nw, mode=mode, out=dst)
+                ms = event_ms([lambda s=s, d=d: call(s, d) for s, d in zip(sets, o)], a.reps)
+                name = mode + ("_static_bg" if static_bg else "") + ("_static_new" if static_nw else "")
+                out[name] = rate(compose_bytes(px, hw, mode, static_bg, static_nw), ms)
+            s = sets[0]
+            nw = s["nw"] if mode == "over" else None
+            assert torch.equal(torch_compose(s["alpha"], s["cmp"], s["bg"], nw, mode),
+                               ops.matte_compose(s["alpha"], s["cmp"], s["bg"], nw, mode=mode)), mode
+            ms_t = event_ms([lambda s=s: torch_compose(s["alpha"], s["cmp"], s["bg"], s["nw"] if mode == "over" else None,
+                                                       mode) for s in sets], a.reps)
+            out["torch_route_" + mode] = {"ms": round(ms_t, 4)}
+            out["speedup_over_torch_" + mode] = round(ms_t / out[mode]["ms"], 1)
+            del o
+        return out
+    res["kernels"] = step("compose kernels", a.step_limit, kernels)
+    del sets
+    torch.cuda.empty_cache()
+
+    np.random.seed(0)
+    model = unet.UNetVideo(synthetic_vgg16(0), dtype="bf16", device="cuda").prepare()
+
+    def streamed():
+        rs = np.random.RandomState(1)
+        k = min(F, 2 * n)  # two distinct chunks of host frames, cycled (the source hands out views of them)
+        cmp, bg = (rs.randint(0, 256, (k, h, w, 3), dtype=np.uint8) for _ in range(2))
+        tri = rs.choice(np.array([0, 128, 255], np.uint8), (k, h, w))
+        plate = rs.randint(0, 256, (h, w, 3), dtype=np.uint8)
+
+        def source():
+            for i in range(0, F, n):
+                m = min(n, F - i)
+                o = i % k
+                yield cmp[o:o + m], bg[o:o + m], tri[o:o + m]
+        streams = {"u8": FrameStream(model, h, w, chunk=n, depth=2, out="u8"),
+                   "over": FrameStream(model, h, w, chunk=n, depth=2, out="over", new_bg=plate),
+                   "bgra": FrameStream(model, h, w, chunk=n, depth=2, out="bgra")}
+
+        def run(fs):
+            t0 = time.perf_counter()
+            tot = sum(m.shape[0] for m in fs.run(source()))
+            torch.cuda.synchronize()
+            assert tot == F
+            return (time.perf_counter() - t0) * 1e3
+        times = {name: [] for name in streams}
+        for i in range(1 + max(3, a.reps // 2)):  # interleaved: every round runs each output once; round 0 warms up
+            for name, fs in streams.items():
+                ms = run(fs)
+                if i:
+                    times[name].append(ms)
+        out = {}
+        for name, t in times.items():
+            ms = statistics.median(t)
+            out["frame_stream_bf16_%s_depth2" % name] = {"ms": round(ms, 2), "frames_per_s": round(F / ms * 1e3, 1),
+                                                         "min_ms": round(min(t), 2), "max_ms": round(max(t), 2)}
+        for name in ("over", "bgra"):
+            out["%s_keeps_of_u8" % name] = round(out["frame_stream_bf16_%s_depth2" % name]["frames_per_s"] /
+                                                 out["frame_stream_bf16_u8_depth2"]["frames_per_s"], 3)
+        return out
+    res["streams"] = step("compose streams", a.step_limit, streamed)
+
+    # the download leg grows from 1 to 3 - 4 B per pixel
+    def link():
+        out = {}
+        for c in (1, 3, 4):
+            hq = torch.empty((n, h, w, c), dtype=torch.uint8).pin_memory()
+            dq = torch.empty((n, h, w, c), dtype=torch.uint8, device="cuda")
+            ms = event_ms([lambda: hq.copy_(dq, non_blocking=True)], a.reps)
+            out["d2h_pinned_u8_x%d" % c] = {"ms": round(ms, 3), "GBps": round(px * c / ms / 1e6, 1)}
+        return out
+    res["link"] = step("compose link", a.step_limit, link)
+    merge_json(a.compose_out, "stream_bench", res)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
@@ -82,9 +220,22 @@ def main():
     ap.add_argument("--sets", type=int, default=3, help="buffer sets the kernel timings cycle through")
     ap.add_argument("--step-limit", type=int, default=150)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ingest_stream.json"))
+    ap.add_argument("--compose-out", default=os.path.join(REPO, "profiles", "compose_stream.json"))
+    ap.add_argument("--sections", default="ingest,compose", help="comma-separated: ingest, compose")
     a = ap.parse_args()
+    sections = set(a.sections.split(","))
+    if not sections or sections - {"ingest", "compose"}:
+        raise SystemExit("stream_bench: --sections takes ingest and / or compose, got %r" % a.sections)
     if not torch.cuda.is_available():
         raise SystemExit("stream_bench needs a ROCm GPU")
+    if "ingest" in sections:
+        ingest_section(a)
+        torch.cuda.empty_cache()
+    if "compose" in sections:
+        compose_section(a)
+
+
+def ingest_section(a):
     from vmatting import FrameStream, ops, unet, video
     from vmatting.weights import synthetic_vgg16
     n, h, w, F = a.chunk, a.height, a.width, a.frames

@@ -8,6 +8,12 @@
 // Chunk<T>::pack applies when the pair kernel reads an f32 frame.  The BGR planes are computed directly in double
 // (convert, subtract, convert); the trimap's u / 255.0 - 0.5 comes from a 256-entry table each block builds in double
 // (one f64 division per entry instead of one per pixel).
+//
+// vm_matte_compose applies the matte: with C = a F + (1 - a) B and B known, the BGRA foreground layer (straight or
+// premultiplied, a = q / 255 of the stored 8-bit matte) or the frame over a new plate N, C + (1 - a)(N - B).  All in
+// float64, one rounding at the end (the formulas: include/vmatting.h).  Traffic per pixel: 4 B alpha + 3 B cmp + 3 B
+// bg (+ 3 B new plate) read, 3 or 4 B written = 13 - 16 B; a static plate is re-read from cache.  Same shape as the
+// ingest kernel: 4 pixels per thread, a scalar tail, one pixel per thread when an operand is unaligned.
 #include "vm_common.h"
 
 namespace vm {
@@ -149,6 +155,121 @@ __global__ void __launch_bounds__(256) matte_quantize_kernel(const float* __rest
   }
 }
 
+// ---------------------------------------------------------------- the matte applied (vm_matte_compose)
+struct ComposeArgs {
+  const float* alpha;
+  const uint8_t* cmp;
+  const uint8_t* bg;
+  const uint8_t* nw;  // the new plate(s): OVER only
+  uint8_t* out;
+  long total;         // n * h * w
+  long hw;            // pixels per frame (a broadcast plate wraps here)
+  int bg_bcast;       // 1: bg is one [h,w,3] plate under n > 1 frames
+  int nw_bcast;       // likewise for the new plate
+  int vec;            // 1: every operand is aligned for the 4-pixel form
+};
+
+// (uint8) rint(min(max(v, 0), 255)), ties to even; v is never NaN here
+__device__ __forceinline__ uint32_t fin(double v) {
+  v = v > 0.0 ? v : 0.0;
+  v = v < 255.0 ? v : 255.0;
+  return (uint32_t)rint(v);
+}
+
+// One pixel: c / b / nw point at its 3 BGR bytes' values.  Returns B | G << 8 | R << 16 (| A << 24 for the layers).
+template <int MODE>
+__device__ __forceinline__ uint32_t compose1(float alpha, const uint32_t* c, const uint32_t* b, const uint32_t* nw) {
+  uint32_t px = 0;
+  if constexpr (MODE == VM_COMPOSE_OVER) {
+    double a = (double)alpha;
+    a = a >= 0.0 ? a : 0.0;  // NaN and negatives -> 0
+    a = a > 1.0 ? 1.0 : a;
+    const double k = 1.0 - a;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+      px |= fin((double)c[ch] + k * ((double)nw[ch] - (double)b[ch])) << (8 * ch);
+  } else {
+    const uint32_t q = quantize1<8>(alpha);
+    const double qd = (double)q;
+    if constexpr (MODE == VM_COMPOSE_PREMUL) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch)
+        px |= fin((double)c[ch] - ((255.0 - qd) * (double)b[ch]) / 255.0) << (8 * ch);
+    } else if (q != 0) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch)
+        px |= fin((double)b[ch] + (((double)c[ch] - (double)b[ch]) * 255.0) / qd) << (8 * ch);
+    }
+    px |= q << 24;
+  }
+  return px;
+}
+
+// 12 bytes = the 4 BGR pixels from p0 of a plane that is per-frame, or one plate wrapping at hw
+__device__ __forceinline__ void load_plane12(const uint8_t* p, int bcast, long hw, long p0, uint32_t* w) {
+  if (!bcast) {
+    load12(p, p0 * 3, w);
+  } else if (hw % 4 == 0) {  // a 4-pixel group never straddles the plate's end
+    load12(p, (p0 % hw) * 3, w);
+  } else {
+    w[0] = w[1] = w[2] = 0;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) w[i >> 2] |= (uint32_t)p[((p0 + i / 3) % hw) * 3 + i % 3] << ((i & 3) * 8);
+  }
+}
+
+// 4 pixels per thread when a.vec: one float4 of alpha, 3 dwords per u8 plane, one 16-byte (BGRA) or three 4-byte
+// (BGR) stores; then a scalar tail, which is every pixel when an operand is unaligned
+template <int MODE>
+__global__ void __launch_bounds__(256) matte_compose_kernel(const ComposeArgs a) {
+  constexpr bool OVER = MODE == VM_COMPOSE_OVER;
+  const long tid = (long)blockIdx.x * 256 + threadIdx.x, nthreads = (long)gridDim.x * 256;
+  const long groups = a.vec ? a.total / 4 : 0;
+  for (long g = tid; g < groups; g += nthreads) {
+    const long p0 = g * 4;
+    const float4 al = reinterpret_cast<const float4*>(a.alpha)[g];
+    const float av[4] = {al.x, al.y, al.z, al.w};
+    uint32_t wc[3], wb[3], wn[3] = {0, 0, 0};
+    load12(a.cmp, p0 * 3, wc);
+    load_plane12(a.bg, a.bg_bcast, a.hw, p0, wb);
+    if constexpr (OVER) load_plane12(a.nw, a.nw_bcast, a.hw, p0, wn);
+    uint32_t px[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint32_t c[3], b[3], nw[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        c[ch] = byte_of(wc, 3 * j + ch);
+        b[ch] = byte_of(wb, 3 * j + ch);
+        nw[ch] = byte_of(wn, 3 * j + ch);
+      }
+      px[j] = compose1<MODE>(av[j], c, b, nw);
+    }
+    if constexpr (OVER) {
+      uint32_t* o = reinterpret_cast<uint32_t*>(a.out + p0 * 3);
+      o[0] = px[0] | (px[1] << 24);
+      o[1] = (px[1] >> 8) | (px[2] << 16);
+      o[2] = (px[2] >> 16) | (px[3] << 8);
+    } else {
+      reinterpret_cast<uint4*>(a.out)[g] = make_uint4(px[0], px[1], px[2], px[3]);
+    }
+  }
+  for (long pix = groups * 4 + tid; pix < a.total; pix += nthreads) {
+    const long bp = a.bg_bcast ? pix % a.hw : pix, np = a.nw_bcast ? pix % a.hw : pix;
+    uint32_t c[3], b[3], nw[3] = {0, 0, 0};
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      c[ch] = a.cmp[pix * 3 + ch];
+      b[ch] = a.bg[bp * 3 + ch];
+      if constexpr (OVER) nw[ch] = a.nw[np * 3 + ch];
+    }
+    const uint32_t px = compose1<MODE>(a.alpha[pix], c, b, nw);
+    uint8_t* o = a.out + pix * (OVER ? 3 : 4);
+#pragma unroll
+    for (int ch = 0; ch < (OVER ? 3 : 4); ++ch) o[ch] = (uint8_t)(px >> (8 * ch));
+  }
+}
+
 }  // namespace
 }  // namespace vm
 
@@ -205,4 +326,35 @@ extern "C" int vm_matte_quantize(const float* alpha, long pixels, int bits, void
   else
     hipLaunchKernelGGL((matte_quantize_kernel<16>), grid, dim3(256), 0, st, alpha, pixels, groups, out);
   return check_launch("matte_quantize");
+}
+
+extern "C" int vm_matte_compose(const float* alpha, const uint8_t* cmp, const uint8_t* bg, int nb, const uint8_t* new_bg,
+                                int nn, int n, int h, int w, int mode, uint8_t* out, void* stream) {
+  if (!alpha || !cmp || !bg || !out) return fail(VM_EINVAL, "matte_compose: null alpha / cmp / bg / output");
+  if (n <= 0 || h <= 0 || w <= 0) return fail(VM_EINVAL, "matte_compose: bad shape [%d,%d,%d]", n, h, w);
+  if (nb != 1 && nb != n) return fail(VM_EINVAL, "matte_compose: %d backgrounds for %d frames (1 or n)", nb, n);
+  if (mode < VM_COMPOSE_OVER || mode > VM_COMPOSE_PREMUL)
+    return fail(VM_EINVAL, "matte_compose: mode %d (0 over, 1 straight BGRA, 2 premultiplied BGRA)", mode);
+  const bool over = mode == VM_COMPOSE_OVER;
+  if (over && (!new_bg || (nn != 1 && nn != n)))
+    return fail(VM_EINVAL, "matte_compose: over takes a new background, %d plates for %d frames (1 or n)", nn, n);
+  if (!over && (new_bg || nn != 0)) return fail(VM_EINVAL, "matte_compose: a BGRA layer takes no new background");
+  ComposeArgs a{};
+  a.alpha = alpha; a.cmp = cmp; a.bg = bg; a.nw = new_bg; a.out = out;
+  a.hw = (long)h * w;
+  a.total = a.hw * n;
+  a.bg_bcast = nb == 1 && n > 1;
+  a.nw_bcast = over && nn == 1 && n > 1;
+  auto aligned = [](const void* p, uintptr_t to) { return reinterpret_cast<uintptr_t>(p) % to == 0; };
+  a.vec = aligned(alpha, 16) && aligned(cmp, 4) && aligned(bg, 4) && (!over || aligned(new_bg, 4)) &&
+          aligned(out, over ? 4 : 16);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid(grid_for(a.vec ? (a.total + 3) / 4 : a.total, 256, 256 * 32));
+  if (mode == VM_COMPOSE_OVER)
+    hipLaunchKernelGGL((matte_compose_kernel<VM_COMPOSE_OVER>), grid, dim3(256), 0, st, a);
+  else if (mode == VM_COMPOSE_STRAIGHT)
+    hipLaunchKernelGGL((matte_compose_kernel<VM_COMPOSE_STRAIGHT>), grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((matte_compose_kernel<VM_COMPOSE_PREMUL>), grid, dim3(256), 0, st, a);
+  return check_launch("matte_compose");
 }

@@ -21,6 +21,7 @@ VM_F32, VM_BF16, VM_U8, VM_F64, VM_F16 = 0, 1, 2, 3, 4
 ACT = {"none": 0, "relu": 1, "sigmoid": 2, "softmax": 3}
 VM_OK, VM_EINVAL, VM_EUNSUPPORTED, VM_EHIP, VM_EINDEX = 0, -1, -2, -3, -4
 ABI_VERSION = 1
+VM_COMPOSE_OVER, VM_COMPOSE_STRAIGHT, VM_COMPOSE_PREMUL = 0, 1, 2
 
 c_void_p, c_int, c_float, c_long, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long, ctypes.c_size_t
 
@@ -188,6 +189,8 @@ SIGNATURES = [
                            c_float, c_void_p]),
     ("vm_frames_from_u8", c_int, [c_void_p, c_void_p, c_void_p, c_int, P, c_void_p]),
     ("vm_matte_quantize", c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p]),
+    ("vm_matte_compose", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                 c_void_p, c_void_p]),
     ("vm_clip_feed", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, P, P, c_void_p,
                              c_void_p, c_void_p]),
 ]

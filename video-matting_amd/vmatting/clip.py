@@ -8,7 +8,7 @@ backgrounds (often one static plate) and the .flo flows between neighbouring fra
 moves one frame per step through ``depth`` slots:
 
     host arrays -> pinned buffers -> (upload stream) device uint8 + flows -> (compute stream) ops.clip_feed ->
-    UNetSimple.forward_fed -> ops.matte_quantize -> pinned output -> numpy
+    UNetSimple.forward_fed -> ops.matte_quantize | ops.matte_compose -> pinned output -> numpy
 
 The upload of frame t + 1 runs beside the compute of frame t.  The matte never leaves the device between frames: the
 feed kernel of frame t reads the model's f32 output buffer, which still holds alpha[t-1], and the forward that follows
@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .pipeline import Slot, SlotPipeline, check_out, check_static_bg
+from .pipeline import PER_FRAME, Slot, SlotPipeline, check_new_bg, check_out, check_static_bg
 from .unet_simple import UNetSimple
 
 PROMOTE = ("numpy1", "numpy2")
@@ -38,7 +38,8 @@ class _Slot(Slot):
         super().__init__(cs.device, (("cmp", (1, h, w, 3), torch.uint8),
                                      ("bw", (1, h, w, 2), torch.float32),
                                      ("bg", (1, h, w, 3) if cs.static_bg is None else None, torch.uint8),
-                                     ("fw", (1, h, w, 2) if cs.occlusion else None, torch.float32)),
+                                     ("fw", (1, h, w, 2) if cs.occlusion else None, torch.float32),
+                                     ("nw", (1, h, w, 3) if cs.new_bg is PER_FRAME else None, torch.uint8)),
                          1, h, w, cs.out, flag=cs.occlusion)
         self.graphs = {}
 
@@ -60,6 +61,12 @@ class ClipStream(SlotPipeline):
     already yielded stand.  ``out``: "u8" / "u16" mattes (ops.matte_quantize) or the "f32" alpha.  Results lag the
     source by ``depth - 1`` frames.
 
+    ``out`` "over" / "bgra" / "premul" applies each frame's matte with the known background (ops.matte_compose) and
+    yields the uint8 [h,w,3] frame over a new plate, or the [h,w,4] BGRA foreground layer (straight / premultiplied;
+    its alpha channel is the "u8" matte).  "over" takes ``new_bg``: a uint8 [h,w,3] plate (uploaded once), or
+    "per_frame", and then every source item is ``(cmp, bg, backward, forward, new_bg)`` with new_bg uint8 [h,w,3].
+    The compose step only reads the model's output buffer: the recurrence is the one of out="f32".
+
     ``reuse_bg_tower`` with a static plate: the plate's tower (13 VGG feature maps, the same every frame) runs with the
     first frame only; later frames run the cmp and warped-matte towers.  ``stats["bg_tower_evals"]`` counts the frames
     of the last run that ran the background tower.
@@ -68,7 +75,7 @@ class ClipStream(SlotPipeline):
     synchronised, and the exception then propagates; the object can run again."""
 
     def __init__(self, model, h, w, depth=2, static_bg=None, occlusion=False, thresh=15.0, promote="numpy1", out="u8",
-                 graph=True, reuse_bg_tower=True):
+                 graph=True, reuse_bg_tower=True, new_bg=None):
         if not isinstance(model, UNetSimple):
             raise TypeError("ClipStream: the video model is a UNetSimple, got %s" % type(model).__name__)
         if model.dtype not in (torch.bfloat16, torch.float32):
@@ -83,26 +90,30 @@ class ClipStream(SlotPipeline):
         if not thresh >= 0.0:
             raise ValueError("ClipStream: thresh must be a non-negative number, got %r" % (thresh,))
         static_bg = check_static_bg("ClipStream", static_bg, h, w)
+        self.new_bg = check_new_bg("ClipStream", out, new_bg, h, w)
         self.model, self.h, self.w, self.depth = model, h, w, depth
         self.static_bg, self.occlusion, self.thresh, self.promote = static_bg, bool(occlusion), thresh, promote
         self.out, self.graph = out, bool(graph)
         self.reuse_bg_tower = bool(reuse_bg_tower) and static_bg is not None
         self.device = model.device
         self.stats = {"bg_tower_evals": 0, "frames": 0}
-        self._plate = self._buf = None
+        self._plate = self._new_plate = self._buf = None
 
     # ------------------------------------------------------------------ checks (host only)
     def check_item(self, item):
-        """Validate one source item; returns (cmp, bg, backward, forward)."""
-        if not isinstance(item, (tuple, list)) or len(item) != 4:
-            raise ValueError("ClipStream: the source yields (cmp, bg, backward, forward) per frame")
-        cmp, bg, bw, fw = item
+        """Validate one source item; returns (cmp, bg, backward, forward), and new_bg after them with
+        new_bg="per_frame"."""
+        per_frame = self.new_bg is PER_FRAME
+        if not isinstance(item, (tuple, list)) or len(item) != 4 + per_frame:
+            raise ValueError("ClipStream: the source yields (cmp, bg, backward, forward%s) per frame" %
+                             (", new_bg" if per_frame else ""))
+        cmp, bg, bw, fw = item[:4]
         if (bg is None) != (self.static_bg is not None):
             raise ValueError("ClipStream: bg is None exactly when a static_bg was given")
         if (fw is None) == self.occlusion:
             raise ValueError("ClipStream: forward is None exactly when occlusion=False")
         for name, a, dt, c in (("cmp", cmp, np.uint8, 3), ("bg", bg, np.uint8, 3), ("backward", bw, np.float32, 2),
-                               ("forward", fw, np.float32, 2)):
+                               ("forward", fw, np.float32, 2)) + ((("new_bg", item[4], np.uint8, 3),) if per_frame else ()):
             if a is None and name in ("bg", "forward"):
                 continue
             if not isinstance(a, np.ndarray):
@@ -111,7 +122,7 @@ class ClipStream(SlotPipeline):
                 raise TypeError("ClipStream: %s must be %s, got %s" % (name, np.dtype(dt).name, a.dtype))
             if a.shape != (self.h, self.w, c):
                 raise ValueError("ClipStream: %s must be [h,w,%d] = %s, got %s" % (name, c, (self.h, self.w, c), a.shape))
-        return cmp, bg, bw, fw
+        return (cmp, bg, bw, fw, item[4]) if per_frame else (cmp, bg, bw, fw)
 
     def check_alpha0(self, alpha0):
         """The matte before the first frame as f32 [h,w]: f32 as it is, uint8 as f32(u / 255.0) (reader.py:16)."""
@@ -139,6 +150,8 @@ class ClipStream(SlotPipeline):
         self._alpha = self._buf["out"]
         if self.static_bg is not None:
             self._plate = torch.from_numpy(self.static_bg).to(dev)
+        if isinstance(self.new_bg, np.ndarray):
+            self._new_plate = torch.from_numpy(self.new_bg).to(dev)
         self._slots = [_Slot(self) for _ in range(self.depth)]
         torch.cuda.synchronize(dev)  # the plate and the zeroed buffers, before another stream touches them
         if self.graph:
@@ -147,7 +160,7 @@ class ClipStream(SlotPipeline):
                     for towers in sorted({self._towers_of(j) for j in range(i, i + 2 * self.depth, self.depth)}):
                         s.graphs[towers] = self.model.capture_fed(
                             1, self.h, self.w, towers, pre=lambda s=s: self._feed(s),
-                            post=lambda s=s: s.download(self._alpha))
+                            post=lambda s=s: self._download(s))
             torch.cuda.synchronize(dev)
 
     def _needs_setup(self):  # (again when the model ran another shape since: its buffers were replaced)
@@ -158,6 +171,12 @@ class ClipStream(SlotPipeline):
         with torch.cuda.stream(self._compute):
             self._alpha.copy_(torch.from_numpy(self._alpha0).view(1, self.h, self.w, 1))
 
+    def _download(self, s):
+        """The slot's result from the model's output buffer (and, composed, the slot's uint8 inputs), which it only
+        reads."""
+        s.download(self._alpha, s.d_cmp, self._plate if self._plate is not None else s.d_bg,
+                   self._new_plate if self._new_plate is not None else s.d_nw)
+
     def _feed(self, s):
         if s.flag is not None:
             s.flag.zero_()
@@ -165,9 +184,9 @@ class ClipStream(SlotPipeline):
         ops.clip_feed(s.d_cmp, self._plate if self._plate is not None else s.d_bg, self._alpha, s.d_bw, s.d_fw,
                       self.thresh, self.promote, towers=towers, cat=cat, err=s.flag)
 
-    def _submit(self, s, index, cmp, bg, bw, fw):
+    def _submit(self, s, index, cmp, bg, bw, fw, nw=None):
         s.index = index
-        for name, a in (("cmp", cmp), ("bw", bw), ("bg", bg), ("fw", fw)):
+        for name, a in (("cmp", cmp), ("bw", bw), ("bg", bg), ("fw", fw), ("nw", nw)):
             s.stage(name, a, 1)
         with torch.cuda.stream(self._upload):
             s.upload(1)
@@ -182,7 +201,7 @@ class ClipStream(SlotPipeline):
             else:
                 self._feed(s)
                 self.model.forward_fed(1, self.h, self.w, towers)
-                s.download(self._alpha)
+                self._download(s)
             s.done.record(self._compute)
 
     def _retire(self, s):
@@ -193,7 +212,8 @@ class ClipStream(SlotPipeline):
         return s.h_out[0].numpy().copy()
 
     def run(self, source, alpha0):
-        """Generator: one [h,w] matte (numpy, the ``out`` dtype) per source item, in source order."""
+        """Generator: one [h,w] matte (numpy, the ``out`` dtype), or one composed [h,w,3 | 4] uint8 array, per source
+        item, in source order."""
         self._alpha0 = self.check_alpha0(alpha0)
         self.stats = {"bg_tower_evals": 0, "frames": 0}
         yield from super().run(source)

@@ -963,6 +963,53 @@ def matte_quantize(alpha, out=None, bits=8):
     return out
 
 
+COMPOSE_MODES = {"over": _lib.VM_COMPOSE_OVER, "bgra": _lib.VM_COMPOSE_STRAIGHT, "premul": _lib.VM_COMPOSE_PREMUL}
+
+
+def matte_compose(alpha, cmp, bg, new_bg=None, mode="over", out=None):
+    """vm_matte_compose: the matte applied, with the known background.  alpha f32 [n,h,w] or [n,h,w,1], cmp u8
+    [n,h,w,3] BGR, bg u8 [n,h,w,3] or one plate [h,w,3] / [1,h,w,3]; all contiguous.  mode "over": the frame over
+    ``new_bg`` (u8, shaped like bg), cmp + (1 - alpha)(new_bg - bg) -> u8 [n,h,w,3]; "bgra" / "premul": the straight /
+    premultiplied foreground layer with the 8-bit matte of matte_quantize as its alpha -> u8 [n,h,w,4] BGRA (no
+    ``new_bg``).  float64 arithmetic, one rounding (include/vmatting.h)."""
+    if mode not in COMPOSE_MODES:
+        raise ValueError("matte_compose: mode must be one of %s, got %r" % (sorted(COMPOSE_MODES), mode))
+    over = mode == "over"
+    if over and new_bg is None:
+        raise ValueError("matte_compose: mode 'over' needs new_bg")
+    if not over and new_bg is not None:
+        raise ValueError("matte_compose: mode %r takes no new_bg" % mode)
+    if not isinstance(alpha, torch.Tensor):
+        raise TypeError("matte_compose: alpha must be a torch tensor, got %s" % type(alpha).__name__)
+    if alpha.dtype != torch.float32:
+        raise TypeError("matte_compose: alpha must be float32, got %s" % alpha.dtype)
+    n, h, w, nb = _check_u8_frames(cmp, bg, None)
+    if tuple(alpha.shape) not in ((n, h, w), (n, h, w, 1)):
+        raise ValueError("matte_compose: alpha must be [n,h,w] or [n,h,w,1] for cmp %s, got %s" %
+                         (tuple(cmp.shape), tuple(alpha.shape)))
+    nn = 0
+    if over:
+        if str(new_bg.dtype).split(".")[-1] != "uint8":
+            raise TypeError("new_bg must be uint8, got %s" % new_bg.dtype)
+        if tuple(new_bg.shape) not in ((n, h, w, 3), (1, h, w, 3), (h, w, 3)):
+            raise ValueError("new_bg must be [n,h,w,3], or one [h,w,3] plate, for cmp %s; got %s" %
+                             (tuple(cmp.shape), tuple(new_bg.shape)))
+        nn = n if tuple(new_bg.shape) == (n, h, w, 3) else 1
+    c = 3 if over else 4
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, c)):
+        raise ValueError("matte_compose: out must be uint8 [n,h,w,%d] = %s, got %s %s" %
+                         (c, (n, h, w, c), out.dtype, tuple(out.shape)))
+    for t in (alpha, cmp, bg) + ((new_bg,) if over else ()) + (() if out is None else (out,)):
+        _require_gpu(t)
+        if not t.is_contiguous():
+            raise ValueError("matte_compose: contiguous tensors expected")
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.uint8, device=cmp.device)
+    check(lib().vm_matte_compose(_ptr(alpha), _ptr(cmp), _ptr(bg), nb, _ptr(new_bg), nn, n, h, w, COMPOSE_MODES[mode],
+                                 _ptr(out), stream_handle()), "matte_compose")
+    return out
+
+
 def clip_feed(cmp, bg, prev_alpha, backward, forward=None, thresh=15.0, promote="numpy1", towers=None, cat=None,
               warped=None, err=None):
     """vm_clip_feed: the video model's feed in one pass.  cmp u8 [n,h,w,3] BGR, bg u8 [n,h,w,3] or one plate [h,w,3] /

@@ -11,7 +11,11 @@ import torch
 
 from . import ops
 
-OUT_DTYPES = {"u8": (np.uint8, torch.uint8, 8), "u16": (np.uint16, torch.uint16, 16), "f32": (np.float32, None, 0)}
+OUT_DTYPES = {"u8": (np.uint8, torch.uint8, 8), "u16": (np.uint16, torch.uint16, 16), "f32": (np.float32, None, 0),
+              # the matte applied (ops.matte_compose): the frame over a new plate, the straight / premultiplied layer
+              "over": (np.uint8, torch.uint8, 8), "bgra": (np.uint8, torch.uint8, 8), "premul": (np.uint8, torch.uint8, 8)}
+COMPOSE_CHANNELS = {"over": 3, "bgra": 4, "premul": 4}  # out -> channels of the composed result
+PER_FRAME = "per_frame"
 
 
 def check_out(who, out):
@@ -20,23 +24,40 @@ def check_out(who, out):
     return out
 
 
-def check_static_bg(who, static_bg, h, w):
+def check_static_bg(who, static_bg, h, w, name="static_bg"):
     """``static_bg`` as a contiguous uint8 [h,w,3] array (None stays None)."""
     if static_bg is None:
         return None
     static_bg = np.asarray(static_bg)
     if static_bg.dtype != np.uint8:
-        raise TypeError("%s: static_bg must be uint8, got %s" % (who, static_bg.dtype))
+        raise TypeError("%s: %s must be uint8, got %s" % (who, name, static_bg.dtype))
     if static_bg.shape != (h, w, 3):
-        raise ValueError("%s: static_bg must be [h,w,3] = %s, got %s" % (who, (h, w, 3), static_bg.shape))
+        raise ValueError("%s: %s must be [h,w,3] = %s, got %s" % (who, name, (h, w, 3), static_bg.shape))
     return np.ascontiguousarray(static_bg)
+
+
+def check_new_bg(who, out, new_bg, h, w):
+    """The new plate of out="over": the string "per_frame" (every source item carries its plates) or a contiguous
+    uint8 [h,w,3] array; None for every other ``out``, which takes none."""
+    if out != "over":
+        if new_bg is not None:
+            raise ValueError("%s: new_bg goes with out='over', not out=%r" % (who, out))
+        return None
+    if new_bg is None:
+        raise ValueError("%s: out='over' needs new_bg: a uint8 [h,w,3] plate or %r" % (who, PER_FRAME))
+    if isinstance(new_bg, str):
+        if new_bg != PER_FRAME:
+            raise ValueError("%s: new_bg must be a uint8 [h,w,3] plate or %r, got %r" % (who, PER_FRAME, new_bg))
+        return PER_FRAME
+    return check_static_bg(who, new_bg, h, w, name="new_bg")
 
 
 class Slot:
     """One item in flight.  ``pairs``: (name, shape | None, dtype) per input; each gives a pinned ``h_<name>`` and its
     device copy ``d_<name>`` (both None for a None shape: an input this configuration does not take).  ``q`` [n,h,w]
-    is the quantised matte (None for out="f32") and ``h_out`` its pinned copy; ``flag`` / ``h_flag`` an int32 [1] pair
-    (None without ``flag``); ``uploaded`` / ``done`` the events of the item's upload and of its compute chain."""
+    is the quantised matte (None for out="f32"), or [n,h,w,C] the composed result (out "over": C = 3, "bgra" /
+    "premul": C = 4), and ``h_out`` its pinned copy; ``flag`` / ``h_flag`` an int32 [1] pair (None without ``flag``);
+    ``uploaded`` / ``done`` the events of the item's upload and of its compute chain."""
 
     def __init__(self, device, pairs, n, h, w, out, flag):
         pin = lambda shape, dt: torch.zeros(shape, dtype=dt).pin_memory()  # noqa: E731
@@ -46,8 +67,10 @@ class Slot:
             setattr(self, "h_" + name, None if shape is None else pin(shape, dt))
             setattr(self, "d_" + name, None if shape is None else gpu(shape, dt))
         _, t_dt, self._bits = OUT_DTYPES[out]
-        self.q = None if t_dt is None else gpu((n, h, w), t_dt)
-        self.h_out = pin((n, h, w), t_dt or torch.float32)
+        self._mode = out if out in COMPOSE_CHANNELS else None
+        shape = (n, h, w) + ((COMPOSE_CHANNELS[out],) if self._mode else ())
+        self.q = None if t_dt is None else gpu(shape, t_dt)
+        self.h_out = pin(shape, t_dt or torch.float32)
         self.flag = gpu((1,), torch.int32) if flag else None
         self.h_flag = pin((1,), torch.int32) if flag else None
         self.uploaded, self.done = torch.cuda.Event(), torch.cuda.Event()
@@ -63,12 +86,15 @@ class Slot:
         for name in self._names:
             getattr(self, "d_" + name)[:k].copy_(getattr(self, "h_" + name)[:k], non_blocking=True)
 
-    def download(self, alpha):
-        """Quantise ``alpha`` ([k,h,w,1] f32) and queue it, and the flag, to the pinned outputs, on the current
-        stream."""
+    def download(self, alpha, cmp=None, bg=None, new_bg=None):
+        """Quantise ``alpha`` ([k,h,w,1] f32), or compose it with ``cmp``, ``bg`` (and ``new_bg``) in the out modes of
+        ops.matte_compose, and queue the result, and the flag, to the pinned outputs, on the current stream."""
         k = alpha.shape[0]
         if self.q is None:
             self.h_out[:k].copy_(alpha[:, :, :, 0], non_blocking=True)
+        elif self._mode:
+            ops.matte_compose(alpha, cmp, bg, new_bg, mode=self._mode, out=self.q[:k])
+            self.h_out[:k].copy_(self.q[:k], non_blocking=True)
         else:
             ops.matte_quantize(alpha, out=self.q[:k], bits=self._bits)
             self.h_out[:k].copy_(self.q[:k], non_blocking=True)

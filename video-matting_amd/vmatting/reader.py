@@ -53,6 +53,44 @@ def create_composite_image(fg, bg, alpha, out_dtype=torch.float64):
     return a * np.asarray(fg) + (1.0 - a) * np.asarray(bg)
 
 
+def _compose_frame(cmp, bg, alpha, new_bg, mode):
+    """One host frame through ops.matte_compose: uint8 [h,w,3] cmp / bg (/ new_bg), alpha f32 or f64 [h,w]."""
+    from vmatting import ops
+    alpha = np.asarray(alpha)
+    if alpha.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("alpha must be float32 or float64, got %s" % alpha.dtype)
+    planes = [np.asarray(a) for a in (cmp, bg) + (() if new_bg is None else (new_bg,))]
+    for name, a in zip(("cmp", "bg", "new_bg"), planes):
+        if a.dtype != np.uint8:
+            raise TypeError("%s must be uint8, got %s" % (name, a.dtype))
+        if a.ndim != 3 or a.shape[2] != 3 or a.shape != planes[0].shape:
+            raise ValueError("%s must be [h,w,3] like cmp %s, got %s" % (name, planes[0].shape, a.shape))
+    if alpha.shape != planes[0].shape[:2]:
+        raise ValueError("alpha must be [h,w] = %s, got %s" % (planes[0].shape[:2], alpha.shape))
+    dev = [torch.from_numpy(np.ascontiguousarray(a)[None]).cuda() for a in planes]
+    a32 = torch.from_numpy(np.ascontiguousarray(alpha.astype(np.float32))[None]).cuda()
+    return ops.matte_compose(a32, dev[0], dev[1], dev[2] if len(dev) == 3 else None, mode=mode)[0].cpu().numpy()
+
+
+def estimate_foreground(cmp, bg, alpha, premultiplied=False):
+    """The inverse of create_composite_image for a known background: the foreground layer of one frame as uint8
+    [h,w,4] BGRA, its alpha channel the 8-bit matte q = rint(alpha * 255).  Straight (the default) is
+    bg + (cmp - bg) * 255 / q, zero where q = 0: the layout of the reference's foreground files (data.create_bgra), so
+    cv2.imwrite of it is a file read_fg_img reads back.  ``premultiplied``: cmp - (255 - q) * bg / 255, the form
+    compositors take.  cmp, bg uint8 [h,w,3] BGR; alpha f32 or f64 [h,w] (f64 is rounded to f32 first).  numpy in ->
+    numpy out, through the vm_matte_compose kernel (float64 arithmetic, one rounding)."""
+    return _compose_frame(cmp, bg, alpha, None, "premul" if premultiplied else "bgra")
+
+
+def replace_background(cmp, bg, alpha, new_bg):
+    """One frame moved onto another plate: cmp + (1 - alpha) * (new_bg - bg) as uint8 [h,w,3] BGR, exact where the
+    frame is a composite over bg (no foreground estimate, no division; the old plate does not bleed through at partly
+    transparent pixels as it does in alpha * cmp + (1 - alpha) * new_bg).  cmp, bg, new_bg uint8 [h,w,3]; alpha f32 or
+    f64 [h,w] (f64 is rounded to f32 first), clamped to [0,1].  numpy in -> numpy out, through the vm_matte_compose
+    kernel (float64 arithmetic, one rounding)."""
+    return _compose_frame(cmp, bg, alpha, new_bg, "over")
+
+
 def read_fg_img(img_path):
     """reader.read_fg_img (reader.py:10-18) via PIL: returns (alpha in [0,1] float64, BGR uint8)."""
     from PIL import Image

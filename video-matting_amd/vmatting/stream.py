@@ -5,7 +5,7 @@ a uint8 BGR background (often one static plate) and uint8 trimaps in host memory
 mattes back.  FrameStream moves chunks of such frames through ``depth`` slots:
 
     host arrays -> pinned buffers -> (upload stream) device uint8 -> (compute stream) ops.frames_from_u8 ->
-    UNet.forward -> ops.matte_quantize -> pinned output -> numpy
+    UNet.forward -> ops.matte_quantize | ops.matte_compose -> pinned output -> numpy
 
 The upload of chunk i + 1 runs beside the compute of chunk i; the download is the tail of each chunk's compute chain.
 A full chunk's chain (ingest, forward, quantise, download) is one HIP graph per slot, captured once over the slot's
@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .pipeline import OUT_DTYPES, Slot, SlotPipeline, check_out, check_static_bg  # noqa: F401  (OUT_DTYPES: public)
+from .pipeline import OUT_DTYPES  # noqa: F401  (public)
+from .pipeline import PER_FRAME, Slot, SlotPipeline, check_new_bg, check_out, check_static_bg
 from .split6 import rerun_x6
 
 
@@ -33,7 +34,8 @@ class _Slot(Slot):
         u8 = torch.uint8
         super().__init__(fs.device, (("cmp", (n, h, w, 3), u8),
                                      ("bg", (n, h, w, 3) if fs.static_bg is None else None, u8),
-                                     ("tri", (n, h, w) if fs.trimap else None, u8)),
+                                     ("tri", (n, h, w) if fs.trimap else None, u8),
+                                     ("nw", (n, h, w, 3) if fs.new_bg is PER_FRAME else None, u8)),
                          n, h, w, fs.out, flag=fs.model.split_mode == "f16x3")  # f16x3: this slot's range flag
         self.frames = ops.frame_buffer(fs.model, n, h, w)
         self.alpha = torch.empty((n, h, w, 1), dtype=torch.float32, device=fs.device)
@@ -48,13 +50,18 @@ class FrameStream(SlotPipeline):
     1 <= k <= chunk.  ``bg`` is None exactly when ``static_bg`` (uint8 [h,w,3], uploaded once) was given; ``trimap`` is
     None exactly when ``trimap=False`` (a 6-channel UNetImage).  An item's arrays are copied before the next item is
     asked for, so the source may reuse them.  ``out``: "u8" / "u16" mattes (ops.matte_quantize) or the "f32" alpha.
+
+    ``out`` "over" / "bgra" / "premul" applies the matte with the known background (ops.matte_compose) and yields uint8
+    [k,h,w,3] frames over a new plate, or [k,h,w,4] BGRA foreground layers (straight / premultiplied; their alpha
+    channel is the "u8" matte).  "over" takes ``new_bg``: a uint8 [h,w,3] plate (uploaded once), or "per_frame", and
+    then every source item is ``(cmp, bg, trimap, new_bg)`` with new_bg uint8 [k,h,w,3].
     Results lag the source by ``depth - 1`` chunks.  On an f16x3 model a chunk whose activations leave fp16's range is
     run again on bf16x6 before it is yielded and its index is appended to ``overflowed_chunks``.
 
     If the source raises, or yields a wrong shape, dtype or k, the chunks already taken are finished and yielded, the
     streams are synchronised, and the exception then propagates; the object can run again."""
 
-    def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True):
+    def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True, new_bg=None):
         h, w, chunk, depth = int(h), int(w), int(chunk), int(depth)
         if h < 1 or w < 1 or chunk < 1 or depth < 1:
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
@@ -64,19 +71,22 @@ class FrameStream(SlotPipeline):
             raise ValueError("FrameStream: %s takes %d channels, so trimap must be %s" %
                              (type(model).__name__, model.IN_CH, model.IN_CH == 7))
         static_bg = check_static_bg("FrameStream", static_bg, h, w)
+        self.new_bg = check_new_bg("FrameStream", out, new_bg, h, w)
         self.model, self.h, self.w, self.chunk, self.depth = model, h, w, chunk, depth
         self.trimap, self.static_bg, self.out, self.graph = bool(trimap), static_bg, out, bool(graph)
         self.device = model.device
         self.overflowed_chunks = []
-        self._plate = None
+        self._plate = self._new_plate = None
         self._x6 = None
 
     # ------------------------------------------------------------------ checks (host only)
     def check_item(self, item):
-        """Validate one source item; returns (cmp, bg, trimap, k)."""
-        if not isinstance(item, (tuple, list)) or len(item) != 3:
-            raise ValueError("FrameStream: the source yields (cmp, bg, trimap) triples")
-        cmp, bg, tri = item
+        """Validate one source item; returns (cmp, bg, trimap, k), and new_bg after them with new_bg="per_frame"."""
+        per_frame = self.new_bg is PER_FRAME
+        if not isinstance(item, (tuple, list)) or len(item) != 3 + per_frame:
+            raise ValueError("FrameStream: the source yields (cmp, bg, trimap%s)" %
+                             (", new_bg) with new_bg='per_frame'" if per_frame else ") triples"))
+        cmp, bg, tri = item[:3]
         if not isinstance(cmp, np.ndarray):
             raise TypeError("FrameStream: cmp must be a numpy array, got %s" % type(cmp).__name__)
         if (bg is None) != (self.static_bg is not None):
@@ -93,6 +103,15 @@ class FrameStream(SlotPipeline):
             raise ValueError("FrameStream: bg must be [k,h,w,3] like cmp, got %s" % (tuple(bg.shape),))
         if k > self.chunk:
             raise ValueError("FrameStream: an item of %d frames exceeds chunk=%d" % (k, self.chunk))
+        if per_frame:
+            nw = item[3]
+            if not isinstance(nw, np.ndarray):
+                raise TypeError("FrameStream: new_bg must be a numpy array, got %s" % type(nw).__name__)
+            if nw.dtype != np.uint8:
+                raise TypeError("FrameStream: new_bg must be uint8, got %s" % nw.dtype)
+            if nw.shape != cmp.shape:
+                raise ValueError("FrameStream: new_bg must be [k,h,w,3] like cmp, got %s" % (tuple(nw.shape),))
+            return cmp, bg, tri, k, nw
         return cmp, bg, tri, k
 
     # ------------------------------------------------------------------ device side
@@ -101,15 +120,23 @@ class FrameStream(SlotPipeline):
         self._make_streams()
         if self.static_bg is not None:
             self._plate = torch.from_numpy(self.static_bg).to(self.device)
+        if isinstance(self.new_bg, np.ndarray):
+            self._new_plate = torch.from_numpy(self.new_bg).to(self.device)
         self._slots = [_Slot(self) for _ in range(self.depth)]
-        torch.cuda.synchronize(self.device)  # the plate and the zeroed pad channels, before another stream reads them
+        torch.cuda.synchronize(self.device)  # the plates and the zeroed pad channels, before another stream reads them
+
+    def _download(self, s, k):
+        """The result of the slot's first k frames from its alpha (and, composed, its uint8 inputs)."""
+        bg = self._plate if self._plate is not None else s.d_bg[:k]
+        nw = self._new_plate if self._new_plate is not None else None if s.d_nw is None else s.d_nw[:k]
+        s.download(s.alpha[:k], s.d_cmp[:k], bg, nw)
 
     def _chain(self, s, k):
-        """Ingest -> forward -> quantise -> download of the slot's first k frames, on the current stream."""
+        """Ingest -> forward -> quantise | compose -> download of the slot's first k frames, on the current stream."""
         bg = self._plate if self._plate is not None else s.d_bg[:k]
         ops.frames_from_u8(s.d_cmp[:k], bg, None if s.d_tri is None else s.d_tri[:k], out=s.frames[:k])
         self.model.forward(s.frames[:k], out=s.alpha[:k], overflow=s.flag)
-        s.download(s.alpha[:k])
+        self._download(s, k)
 
     def _capture(self, s):
         """The full-chunk chain of one slot as one HIP graph: UNet.capture records the forward over the slot's static
@@ -118,11 +145,11 @@ class FrameStream(SlotPipeline):
         s.graph = self.model.capture(
             s.frames, static=True, out=s.alpha, overflow=s.flag,
             pre=lambda: ops.frames_from_u8(s.d_cmp, bg, s.d_tri, out=s.frames),
-            post=lambda: s.download(s.alpha))
+            post=lambda: self._download(s, self.chunk))
 
-    def _submit(self, s, index, cmp, bg, tri, k):
+    def _submit(self, s, index, cmp, bg, tri, k, nw=None):
         s.k, s.index = k, index
-        for name, a in (("cmp", cmp), ("bg", bg), ("tri", tri)):
+        for name, a in (("cmp", cmp), ("bg", bg), ("tri", tri), ("nw", nw)):
             s.stage(name, a, k)
         with torch.cuda.stream(self._upload):
             s.upload(k)
@@ -146,11 +173,12 @@ class FrameStream(SlotPipeline):
             with torch.cuda.stream(self._compute):
                 rerun_x6(self, s.frames[:k], s.alpha[:k])
                 s.flag.zero_()
-                s.download(s.alpha[:k])
+                self._download(s, k)
             self._compute.synchronize()
         return s.h_out[:k].numpy().copy()
 
     def run(self, source):
-        """Generator: one [k,h,w] matte (numpy, the ``out`` dtype) per source item, in source order."""
+        """Generator: one [k,h,w] matte (numpy, the ``out`` dtype), or one composed [k,h,w,3 | 4] uint8 array, per source
+        item, in source order."""
         self.overflowed_chunks = []
         yield from super().run(source)
