@@ -1,5 +1,5 @@
 // Conv argument block and device helpers shared by the 3x3 conv kernels (conv3x3.hip, conv_rows.hip, conv_pair.hip,
-// conv_first.hip, conv_head.hip) and train.hip's MFMA kernels.  Device code only: the host side (options, launchers) is conv_dispatch.h.
+// conv_first.hip, conv_head.hip) and wgrad.hip's MFMA kernels.  Device code only: the host side (options, launchers) is conv_dispatch.h.
 #pragma once
 
 #include <type_traits>
