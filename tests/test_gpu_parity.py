@@ -774,6 +774,32 @@ def test_up2x_head_partials(shape, store_y):
     assert float((a_sp - a_full).abs().max()) < 1e-5
 
 
+@pytest.mark.parametrize("shape", [(2, 8, 16), (1, 17, 23)])
+def test_up2x_head_state_ends_with_its_call(shape):
+    """The head split's arguments (partials, store_y = 0) belong to the vm_conv3x3_up2x_head_nhwc call alone: a plain
+    vm_conv3x3_up2x_nhwc after it writes the same y, bit for bit, as one before it, and the head call itself leaves
+    its y at the sentinel."""
+    from vmatting import ops
+    n, h, w = shape
+    rs = np.random.RandomState(h * w + n)
+    x = torch.from_numpy(rs.uniform(0, 2, (n, h, w, 128)).astype(np.float32)).to(DEV).to(torch.bfloat16)
+    pc = ops.PackedConv((rs.normal(size=(3, 3, 128, 64)) * np.sqrt(2.0 / 1152)).astype(np.float32), None,
+                        torch.bfloat16, DEV)
+    whd = T((rs.normal(size=(3, 3, 128, 1)) * np.sqrt(2.0 / 1152)).astype(np.float32))
+
+    def sentinel():
+        return torch.full((n, 2 * h, 2 * w, 64), 7.0, dtype=torch.bfloat16, device=DEV)
+
+    before, yh, after = sentinel(), sentinel(), sentinel()
+    part = torch.full((n, 2 * h, 2 * w, 12), 3.0, dtype=torch.float32, device=DEV)
+    ops.upconv3x3(x, pc, "none", out=before)
+    assert ops.upconv3x3_head(x, pc, whd, 0, part, "none", out=yh, store_y=False) is not None
+    ops.upconv3x3(x, pc, "none", out=after)
+    assert torch.equal(before, after)
+    assert not torch.equal(before, sentinel())  # (the plain call did write y)
+    assert float((yh.float() - 7.0).abs().max()) == 0.0
+
+
 def test_unet_bf16_fused_and_unfused_forward_agree(vgg0):
     """bf16 forward: fusing conv1_1->conv1_2 changes nothing (bit for bit, the lazily evaluated .conv1_1 included);
     folding the upconv resizes stays in the bf16 error class of the resize + conv path (logits; alpha of saturated

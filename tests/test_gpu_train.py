@@ -1097,7 +1097,7 @@ def test_side_streams_bit_identical_bench_shape():
     """the select chains write channel slices of the concat rows on side streams while the main stream's
     upconv writes the neighbouring channels.  Every epilogue on this path (patch / thin / split-K reduce / bn_apply)
     stores only inside its channel view: a whole 16-byte chunk only when the view is 16-byte aligned and the chunk
-    lies inside [coff, coff + c) (conv3x3.hip: y_vec && co + 8 <= cout), element-wise otherwise (upconv1 at channel
+    lies inside [coff, coff + c) (conv3x3.hip's generic kernels: y_vec && co + 8 <= cout; conv_patch.hip: patch_ok), element-wise otherwise (upconv1 at channel
     6 of its concat, the 2..16-channel selects) -- no read-modify-write of a neighbour's bytes.  Checked at the bench's 8 x 320^2 bf16 batch, where the kernels do overlap in time: three steps
     with side streams and three on one stream leave bit-identical losses and variables."""
     from vmatting.train import VideoTrainer

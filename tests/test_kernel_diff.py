@@ -66,3 +66,9 @@ def test_shipped_library_equals_itself():
     assert len(same) >= 1 and len(same) == len(k)
     assert not only_a and not only_b and not differ
     assert any("conv3x3_first_softmax_strip" in n for n in k) and any("conv3x3_head_mfma" in n for n in k)
+    # one kernel of each conv unit split off conv3x3.hip (conv_patch, conv_thin, conv_pack, conv_up2x) and of conv_pair
+    for name in ("conv3x3_patch_persist", "conv3x3_thin", "pack_weights_tiled", "conv3x3_up2x_border",
+                 "conv3x3_pair_persist"):
+        assert any(name in n for n in k), name
+    # ... and no kernel defined in two units (a second copy is keyed "name#2"): the one every unit reaches
+    assert sum("splitk_reduce_kernel" in n for n in k) == 1

@@ -1,5 +1,5 @@
-// Conv argument block and device helpers shared by the 3x3 conv kernels (conv3x3.hip, conv_rows.hip, conv_pair.hip,
-// conv_first.hip, conv_head.hip) and wgrad.hip's MFMA kernels.  Device code only: the host side (options, launchers) is conv_dispatch.h.
+// Conv argument block and device helpers shared by the 3x3 conv kernels (conv3x3.hip and every conv_*.hip) and
+// wgrad.hip's MFMA kernels.  Device code only: the host side (options, launchers) is conv_dispatch.h.
 #pragma once
 
 #include <type_traits>
@@ -103,6 +103,28 @@ __device__ __forceinline__ long src_chan(const ConvArgs& a, int c) {
   if (a.x_src_c <= 0) return c;
   const int s = c / a.x_src_c;
   return (long)s * a.x_src_stride + (c - s * a.x_src_c);
+}
+
+// (K element index k) -> (tap, channel); tap 9 = padding (contributes zero)
+template <int GE>
+__device__ __forceinline__ void k_to_tap(const ConvArgs& a, int k, int& tap, int& c) {
+  if (a.chunk_major) {
+    const int g = k / GE;
+    if (g < a.ng) {
+      const int cc = g / 9;
+      tap = g - cc * 9;
+      c = cc * GE + (k - g * GE);
+    } else {
+      tap = 9;
+      c = 0;
+    }
+  } else if (k < a.K9) {
+    tap = k / a.cin_pad;
+    c = k - tap * a.cin_pad;
+  } else {
+    tap = 9;
+    c = 0;
+  }
 }
 
 // LDS images are [row][RB bytes] with the 16-byte chunk index XOR-swizzled per row; both swizzles

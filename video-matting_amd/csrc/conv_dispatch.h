@@ -1,6 +1,6 @@
-// Host side of the 3x3 conv translation units (conv3x3.hip, conv_rows.hip, conv_pair.hip, conv_first.hip,
-// conv_head.hip): the tuning options (vm_set_option), the call and filter-geometry structs, and the launchers through
-// which conv3x3.hip's routing reaches the kernels of the other files.
+// Host side of the 3x3 conv translation units (conv3x3.hip and every conv_*.hip): the tuning options (vm_set_option),
+// the call and filter-geometry structs, and the launchers through which one file's routing reaches the kernels of
+// another.
 #pragma once
 
 #include "conv_common.h"
@@ -146,12 +146,27 @@ struct ConvCall {
   const SplitOut* so = nullptr;      // split-fp16 x3 output
 };
 
-// launchers defined in conv_rows.hip (called from conv3x3.hip's dispatch)
+// a split-fp16 view (vm_conv3x3_split3_nhwc, vm_conv3x3_up2x_split3_nhwc): c channels inside the first of two (or
+// three) slabs of slab % 8 == 0 channels, 16-byte aligned
+inline bool split3_view_ok(const vm_tensor* t, int slab, int c) {
+  return t->dtype == VM_F16 && view16_ok(t) && slab > 0 && slab % 8 == 0 && t->coff + c <= slab && 2 * slab <= t->cstride;
+}
+
+// conv_patch.hip (called from conv_impl, dispatch_mfma and conv_up2x.hip); a kernel is launched from its own unit only
+bool patch_ok(const ConvArgs& a, size_t tsize);
+int dispatch_patch(ConvArgs& a, hipStream_t st);
+int splitk_plan(long n, int h, int w, int cin_pad, int cout);
+int launch_splitk_reduce(const ConvArgs& a, hipStream_t st);  // a.part's a.ksplit partial sums -> a.y (conv_thin.hip too)
+int launch_patch_first(ConvArgs& a, hipStream_t st);  // the FIRST patch kernel: conv_pair.hip's streaming fallback
+// conv_thin.hip (called from conv_impl and vm_conv3x3_workspace_bytes)
+bool thin_ok(int dt, const PackGeom& g, int cout, int x_src_c, int act, const vm_tensor* x);
+bool narrowin_ok(const ConvArgs& a, const PackGeom& g, int cout, int act, const vm_tensor* x, const vm_tensor* y);
+int launch_narrowin(ConvArgs& a, long n, const PackGeom& g, hipStream_t st);
+int thin_splitk_plan(long n, int h, int w, int cin_pad);
+int dispatch_thin(ConvArgs& a, long n, hipStream_t st);
+// launchers defined in conv_rows.hip (called from dispatch_patch)
 bool rows_ok(const ConvArgs& a);
 int launch_rows(ConvArgs& a, hipStream_t st, int cfg);
-// launchers defined in conv_pair.hip
-bool pair_strip_ok(const ConvArgs& a);
-int launch_pair_strip(ConvArgs& a, long nimg, hipStream_t st);
 // launchers defined in conv_first.hip (dispatch_mfma decides when they apply)
 int launch_first(ConvArgs& a, hipStream_t st);
 int launch_first_softmax(ConvArgs& a, hipStream_t st);

@@ -56,10 +56,15 @@ inline bool valid_tensor(const vm_tensor* t, bool allow_f16 = false) {
          t->coff + t->c <= t->cstride && (t->dtype == VM_F32 || t->dtype == VM_BF16 || (allow_f16 && t->dtype == VM_F16));
 }
 
+// the view's base, pixel stride and channel offset are whole 16-byte chunks (ve elements; 0: of the view's dtype)
+inline bool view16_ok(const vm_tensor* t, int ve = 0) {
+  if (!ve) ve = 16 / elem_bytes(t->dtype);
+  return (reinterpret_cast<uintptr_t>(t->ptr) % 16 == 0) && (t->cstride % ve == 0) && (t->coff % ve == 0);
+}
+
+// ... and so is its channel count
 inline bool vec16_ok(const vm_tensor* t, int extra_elems_multiple = 1) {
-  int ve = 16 / elem_bytes(t->dtype);
-  return (reinterpret_cast<uintptr_t>(t->ptr) % 16 == 0) && (t->cstride % ve == 0) && (t->coff % ve == 0) &&
-         (t->c % (ve * extra_elems_multiple) == 0);
+  return view16_ok(t) && t->c % (16 / elem_bytes(t->dtype) * extra_elems_multiple) == 0;
 }
 
 // ---------------------------------------------------------------- device helpers

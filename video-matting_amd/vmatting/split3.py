@@ -80,7 +80,7 @@ def split3_filter(w_hwio, cin, cout, t):
 
 
 # TF-1 legacy bilinear 2x (scale 0.5) as a phase filter: resized row 2i + a blends low-res rows by R[a] (rows: the
-# low-res tap u = offset u - 1, columns: the 3x3 kernel row kh), the same table as csrc/conv3x3.hip fold_up2x_weights
+# low-res tap u = offset u - 1, columns: the 3x3 kernel row kh), the same table as csrc/conv_up2x.hip fold_up2x_weights
 _R = np.array([[[.5, 0., 0.], [.5, 1., .5], [0., 0., .5]], [[0., 0., 0.], [1., .5, 0.], [0., .5, 1.]]])
 
 
