@@ -660,6 +660,44 @@ int vm_clip_feed(const uint8_t* cmp, const uint8_t* bg, int nb, const float* pre
                  const float* forward, float thresh, int promote, vm_tensor* towers, vm_tensor* cat, float* warped,
                  int* err_flag, void* stream);
 
+/* ---------------------------------------------------------------- dense two-frame optical flow
+ * The flow vm_clip_feed consumes, estimated from two decoded frames instead of read from .flo files (the reference
+ * computes none: no counterpart there).  estimate(cur, prev) = f with cur(x, y) ~ prev(x + f[..,0], y + f[..,1]): the
+ * "backward" flow of a frame into the one before it, reader.read_flow layout; the forward flow is estimate(prev, cur).
+ * Coarse-to-fine Horn-Schunck with warping and Jacobi sweeps, all f32, nothing contracted, in exactly this order:
+ *   grey      g = f32(29 B + 150 G + 77 R) / 256.f
+ *   pyramid   level 0 = g; level k+1 = ((a00 + a01) + (a10 + a11)) * 0.25f over 2x2 of level k, ceil sizes, the last
+ *             row / column replicated; a level is added while fewer than `levels` exist and min(h_k, w_k) / 2 >= 8
+ *   smooth    afterwards each level once by [1/4 1/2 1/4], horizontally r = (l + r) * 0.25f + c * 0.5f, then vertically
+ *             the same on the result, replicate borders (levels are built from the unsmoothed level below)
+ *   bilinear  x clamped to [0, w-1], y to [0, h-1]; x0 = floor, x1 = min(x0 + 1, w - 1); top = p00 + fx * (p01 - p00),
+ *             bot likewise, top + fy * (bot - top)
+ *   level     flow = 0 at the coarsest, else 2.f * bilinear(coarser flow, ((x - 0.5f) * 0.5f, (y - 0.5f) * 0.5f))
+ *   warp      `warps` times per level, (u0, v0) the flow at its start: Iw = bilinear(prev_k, (x + u0, y + v0));
+ *             Ix, Iy = (next - previous) * 0.5f of Iw, replicate borders; It = Iw - cur_k;
+ *             den = (alpha * alpha + Ix * Ix) + Iy * Iy
+ *   sweep     `iters` times per warp, Jacobi (u and v both from the previous iterate, replicate borders):
+ *             ub = ((up + down) + (left + right)) * (1 / 6.f) + ((ul + ur) + (dl + dr)) * (1 / 12.f), vb likewise;
+ *             r = (Ix * (ub - u0) + Iy * (vb - v0)) + It; q = r / den; u = ub - Ix * q, v = vb - Iy * q
+ * tests/flow_est_ref.py restates this in numpy; the kernels match it bit for bit.  The sweeps run FT = 4 per launch
+ * on LDS tiles (csrc/flow_est.hip; vm_set_option "flow_blocked" 0: one sweep per launch, the same bits).
+ *   cur, prev  uint8 [h,w,3] BGR;  flow f32 [h,w,2], 8-byte aligned
+ *   work       vm_flow_estimate_workspace_bytes(h, w, levels) bytes, 16-byte aligned
+ * No allocation and no synchronisation inside: the calls can be captured in a graph.  VM_EINVAL for NULL pointers,
+ * h or w < 16, levels / warps / iters < 1, alpha <= 0 or NaN (checked before any HIP call); the size queries return 0
+ * for such shapes.
+ * The split form shares work between calls: vm_flow_pyramid writes one frame's smoothed levels (vm_flow_pyramid_bytes,
+ * 16-byte aligned; the levels' order and offsets are the library's own) and vm_flow_from_pyramids estimates from two
+ * of them; both take the same workspace as vm_flow_estimate, which is vm_flow_pyramid twice and then
+ * vm_flow_from_pyramids.  The two directions of one frame pair share both pyramids, consecutive pairs share one. */
+size_t vm_flow_estimate_workspace_bytes(int h, int w, int levels);
+int vm_flow_estimate(const uint8_t* cur, const uint8_t* prev, int h, int w, int levels, int warps, int iters,
+                     float alpha, float* flow, void* work, void* stream);
+size_t vm_flow_pyramid_bytes(int h, int w, int levels);
+int vm_flow_pyramid(const uint8_t* frame, int h, int w, int levels, float* pyr, void* work, void* stream);
+int vm_flow_from_pyramids(const float* cur, const float* prev, int h, int w, int levels, int warps, int iters,
+                          float alpha, float* flow, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

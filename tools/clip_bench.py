@@ -2,10 +2,13 @@
 and its parts, the host link, and ClipStream from host arrays.  Prints one JSON line and writes it to
 profiles/clip_stream.json.  The compose section (``--sections compose``) runs ClipStream with out="over" (a static
 new plate) beside out="u8" on the same clip, their runs interleaved in one process; it prints a second JSON line and
-writes it under "clip_bench" in profiles/compose_stream.json.
+writes it under "clip_bench" in profiles/compose_stream.json.  The flow section (``--sections flow``) times the flow
+estimator (ops.estimate_flow: the blocked sweep kernel beside the one-sweep-per-launch path, and the time of one
+full-resolution sweep of each) and ClipStream(flow="estimate") beside ClipStream(flow="given") on the same frames; it
+writes profiles/flow_estimate.json.
 
     python tools/clip_bench.py [--sizes 500x1200,1080x1920] [--frames 48] [--reps 9] [--dtype bf16]
-                               [--sections clip,compose]
+                               [--sections clip,compose,flow]
 
 Kernel times are hipEvent medians over ``--reps`` runs after a warm-up; every run of a kernel works on another of
 several buffer sets, so its inputs and outputs do not sit in the 256 MB memory-side cache between runs.  The fused and
@@ -313,6 +316,100 @@ def measure_compose(h, w, a, vgg, params):
     return res
 
 
+def measure_flow(h, w, a, vgg, params):
+    """The flow estimator: one direction with the defaults, blocked against per-sweep (interleaved windows, two buffer
+    sets); one full-resolution sweep of either path, from the difference of two sweep counts at levels=1; and ClipStream
+    with flow="estimate" (with and without occlusion) beside flow="given" fed with the same flows, round-robin."""
+    from vmatting import ClipStream, _lib, ops, unet_simple
+    px = h * w
+    rs = np.random.RandomState(3)
+    # four frames cut from one smooth texture, each 3 px right and 2 px down of the one before
+    tex = rs.uniform(0, 255, (h + 16, w + 16, 3)).astype(np.float32)
+    for _ in range(3):
+        tex = sum(np.roll(tex, (i, j), (0, 1)) for i in (-1, 0, 1) for j in (-1, 0, 1)) / 9.0
+    tex = np.clip((tex - tex.mean()) / tex.std() * 48.0 + 128.0, 0, 255).astype(np.uint8)
+    frames = np.stack([tex[2 * i:2 * i + h, 3 * i:3 * i + w] for i in range(4)])
+    dev = [torch.from_numpy(np.ascontiguousarray(f)).cuda() for f in frames]
+    sets = [dict(cur=dev[i + 1], prev=dev[i], out=torch.empty((h, w, 2), device="cuda"),
+                 work=torch.empty(ops.flow_workspace_bytes(h, w), dtype=torch.uint8, device="cuda")) for i in range(2)]
+
+    def est(s, blocked, **kw):
+        _lib.set_option("flow_blocked", blocked)
+        ops.estimate_flow(s["cur"], s["prev"], out=s["out"], work=s["work"], **kw)
+
+    def kernels():
+        out = {}
+        flows = []
+        for blocked in (1, 0):
+            est(sets[0], blocked)
+            flows.append(sets[0]["out"].clone())
+        assert torch.equal(flows[0].view(torch.int32), flows[1].view(torch.int32)), "blocked and per-sweep flows differ"
+        out["mean_abs_flow_px"] = round(float(flows[0].abs().mean()), 3)
+        ms_b, ms_p = interleaved_ms([lambda s=s: est(s, 1) for s in sets], [lambda s=s: est(s, 0) for s in sets], a.reps)
+        out["estimate_blocked"] = {"ms": round(ms_b, 3)}
+        out["estimate_per_sweep"] = {"ms": round(ms_p, 3)}
+        out["blocked_speedup"] = round(ms_p / ms_b, 2)
+        # one full-resolution sweep: levels=1, warps=3, (iters 40 - iters 20) / 60
+        per = {}
+        for blocked, key in ((1, "blocked"), (0, "per_sweep")):
+            lo, hi = interleaved_ms([lambda s=s: est(s, blocked, levels=1, iters=20) for s in sets],
+                                    [lambda s=s: est(s, blocked, levels=1, iters=40) for s in sets], a.reps)
+            per[key] = (hi - lo) / 60.0
+        # bytes per pixel and sweep: per-sweep 8 (u, v) + 16 (Ix, Iy, It, den) + 8 (u0, v0) read, 8 written; blocked
+        # the same reads for the 64 x 40 staged pixels of a 56 x 32 tile and one write per 4 sweeps
+        model = {"per_sweep": 40.0, "blocked": (32.0 * (64 * 40) / (56 * 32) + 8.0) / 4}
+        for key, ms in per.items():
+            out["sweep_" + key] = dict(rate(px * model[key], ms), us=round(ms * 1e3, 2), model_bytes_per_px=round(model[key], 2))
+        _lib.set_option("flow_blocked", 1)
+        return out
+    res = step("flow kernels %dx%d" % (h, w), a.step_limit, kernels)
+
+    def streamed():
+        np.random.seed(0)
+        model = unet_simple.UNetSimple(unet_simple.Vgg16(vgg, a.dtype), False, a.dtype).load_params(params)
+        F = a.frames
+        bg = rs.randint(0, 256, (h, w, 3), dtype=np.uint8)
+        alpha0 = rs.uniform(size=(h, w)).astype(np.float32)
+        # the flows a caller of flow="given" would bring: frame i against frame i - 1 of the 4-cycle, both directions
+        bw = [ops.estimate_flow(dev[i], dev[i - 1]).cpu().numpy() for i in range(4)]
+        fw = [ops.estimate_flow(dev[i - 1], dev[i]).cpu().numpy() for i in range(4)]
+
+        def source(given, occ):
+            for i in range(F):
+                k = i % 4
+                yield frames[k], bg, (bw[k] if given else None), (fw[k] if given and occ else None)
+        kw = dict(depth=2, out="u8", thresh=a.thresh)
+        streams = {(mode, occ): ClipStream(model, h, w, occlusion=occ, flow=mode, **kw)
+                   for occ in (False, True) for mode in ("given", "estimate")}
+
+        def run(mode, occ):
+            t0 = time.perf_counter()
+            extra = dict(cmp0=frames[3]) if mode == "estimate" else {}
+            tot = sum(1 for _ in streams[mode, occ].run(source(mode == "given", occ), alpha0, **extra))
+            torch.cuda.synchronize()
+            assert tot == F
+            return (time.perf_counter() - t0) * 1e3
+        times = {k: [] for k in streams}
+        for i in range(1 + max(3, a.reps // 3)):  # round 0 warms up (and captures the graphs)
+            for k in streams:
+                ms = run(*k)
+                if i:
+                    times[k].append(ms)
+        out = {}
+        for (mode, occ), t in times.items():
+            ms = statistics.median(t)
+            out["clip_stream_%s%s" % (mode, "_occ" if occ else "")] = {
+                "ms_per_frame": round(ms / F, 3), "frames_per_s": round(F / ms * 1e3, 1),
+                "min_ms_per_frame": round(min(t) / F, 3), "max_ms_per_frame": round(max(t) / F, 3)}
+        for occ in ("", "_occ"):
+            out["estimator_cost_ms_per_frame" + occ] = round(out["clip_stream_estimate" + occ]["ms_per_frame"] -
+                                                             out["clip_stream_given" + occ]["ms_per_frame"], 3)
+        return out
+    res.update(step("flow streamed %dx%d" % (h, w), a.step_limit, streamed))
+    torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="500x1200,1080x1920")
@@ -324,11 +421,12 @@ def main():
     ap.add_argument("--step-limit", type=int, default=150)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "clip_stream.json"))
     ap.add_argument("--compose-out", default=os.path.join(REPO, "profiles", "compose_stream.json"))
-    ap.add_argument("--sections", default="clip,compose", help="comma-separated: clip, compose")
+    ap.add_argument("--flow-out", default=os.path.join(REPO, "profiles", "flow_estimate.json"))
+    ap.add_argument("--sections", default="clip,compose", help="comma-separated: clip, compose, flow")
     a = ap.parse_args()
     sections = set(a.sections.split(","))
-    if not sections or sections - {"clip", "compose"}:
-        raise SystemExit("clip_bench: --sections takes clip and / or compose, got %r" % a.sections)
+    if not sections or sections - {"clip", "compose", "flow"}:
+        raise SystemExit("clip_bench: --sections takes clip, compose and / or flow, got %r" % a.sections)
     if not torch.cuda.is_available():
         raise SystemExit("clip_bench needs a ROCm GPU")
     from oracle import models as om
@@ -357,6 +455,14 @@ def main():
         with open(a.compose_out, "w") as f:
             f.write(json.dumps(doc) + "\n")
         print(json.dumps(res))
+    if "flow" in sections:
+        res = dict(head, hbm_peak_GBps=HBM_PEAK / 1e9,
+                   sizes={"%dx%d" % (h, w): measure_flow(h, w, a, vgg, params) for h, w in sizes})
+        line = json.dumps(res)
+        os.makedirs(os.path.dirname(a.flow_out), exist_ok=True)
+        with open(a.flow_out, "w") as f:
+            f.write(line + "\n")
+        print(line)
 
 
 if __name__ == "__main__":

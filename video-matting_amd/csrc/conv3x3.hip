@@ -757,7 +757,7 @@ static int set_from(const OptDef* t, const char* key, long value) {
 
 extern "C" int vm_set_option(const char* key, long value) {
   if (!key) return fail(VM_EINVAL, "set_option: NULL key");
-  for (const OptDef* t : {conv_options, bn_options, train_options, wgrad_options}) {
+  for (const OptDef* t : {conv_options, bn_options, train_options, wgrad_options, flow_options}) {
     const int rc = set_from(t, key, value);
     if (rc != 1) return rc;
   }

@@ -16,7 +16,7 @@ void set_error(const char* fmt, ...);
 
 // One vm_set_option key: where its value lives and which values it takes.  The files that own options each define a
 // table of these, ended by a null key (conv_options in conv3x3.hip, train_options in train.hip, wgrad_options in
-// wgrad.hip, bn_options in elementwise.hip); vm_set_option walks the four.
+// wgrad.hip, bn_options in elementwise.hip, flow_options in flow_est.hip); vm_set_option walks them.
 enum OptKind {
   OPT_ANY,    // every value
   OPT_RANGE,  // v[0] <= value <= v[1]
@@ -30,7 +30,7 @@ struct OptDef {
   long v[5];
   const char* note;  // appended to the rejection message (may be null)
 };
-extern const OptDef train_options[], wgrad_options[], bn_options[];
+extern const OptDef train_options[], wgrad_options[], bn_options[], flow_options[];
 
 inline int fail(int code, const char* fmt, ...) {
   char buf[512];

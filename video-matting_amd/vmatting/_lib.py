@@ -193,6 +193,13 @@ SIGNATURES = [
                                  c_void_p, c_void_p]),
     ("vm_clip_feed", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, P, P, c_void_p,
                              c_void_p, c_void_p]),
+    ("vm_flow_estimate_workspace_bytes", c_size_t, [c_int, c_int, c_int]),
+    ("vm_flow_estimate", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
+                                 c_void_p]),
+    ("vm_flow_pyramid_bytes", c_size_t, [c_int, c_int, c_int]),
+    ("vm_flow_pyramid", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("vm_flow_from_pyramids", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                      c_void_p, c_void_p]),
 ]
 
 _lib = None

@@ -15,8 +15,10 @@ feed kernel of frame t reads the model's f32 output buffer, which still holds al
 it in stream order overwrites that buffer with alpha[t].  A frame's compute chain (zero the flag, feed, forward,
 quantise, download) is one HIP graph per slot, captured once over static buffers on one stream.
 
-The flows come from the caller, as in the reference's .flo files; so does the matte before the first frame (for
-example a key frame's matte by UNetVideo).
+The flows come from the caller, as in the reference's .flo files, or (``flow="estimate"``) from the frames themselves:
+ops.flow_pyramid of the frame and ops.flow_from_pyramids against the previous frame's pyramid head the frame's chain,
+and nothing is staged or uploaded for the flows.  The matte before the first frame comes from the caller (for example
+a key frame's matte by UNetVideo).
 """
 
 import numpy as np
@@ -27,6 +29,7 @@ from .pipeline import PER_FRAME, Slot, SlotPipeline, check_new_bg, check_out, ch
 from .unet_simple import UNetSimple
 
 PROMOTE = ("numpy1", "numpy2")
+FLOW_MODES = ("given", "estimate")
 
 
 class _Slot(Slot):
@@ -36,9 +39,9 @@ class _Slot(Slot):
     def __init__(self, cs):
         h, w = cs.h, cs.w
         super().__init__(cs.device, (("cmp", (1, h, w, 3), torch.uint8),
-                                     ("bw", (1, h, w, 2), torch.float32),
+                                     ("bw", None if cs.estimate else (1, h, w, 2), torch.float32),
                                      ("bg", (1, h, w, 3) if cs.static_bg is None else None, torch.uint8),
-                                     ("fw", (1, h, w, 2) if cs.occlusion else None, torch.float32),
+                                     ("fw", (1, h, w, 2) if cs.occlusion and not cs.estimate else None, torch.float32),
                                      ("nw", (1, h, w, 3) if cs.new_bg is PER_FRAME else None, torch.uint8)),
                          1, h, w, cs.out, flag=cs.occlusion)
         self.graphs = {}
@@ -71,11 +74,18 @@ class ClipStream(SlotPipeline):
     first frame only; later frames run the cmp and warped-matte towers.  ``stats["bg_tower_evals"]`` counts the frames
     of the last run that ran the background tower.
 
+    ``flow="estimate"``: the flows are estimated on the device from consecutive frames (ops.estimate_flow's
+    arithmetic; ``flow_options``: its levels / warps / iters / alpha) instead of given.  Source items keep their shape
+    with both flows None, ``(cmp, bg, None, None[, new_bg])``; h and w are at least 16.  ``run(source, alpha0, cmp0)``
+    takes the uint8 [h,w,3] frame ``alpha0`` belongs to; with ``cmp0=None``, alpha0 belongs to the first frame itself
+    and that frame's flows are zero.  The mattes are those of ``flow="given"`` fed with ops.estimate_flow(cmp[t],
+    cmp[t-1]) (and, with ``occlusion``, ops.estimate_flow(cmp[t-1], cmp[t])), bit for bit.
+
     If the source raises, or yields a bad item, the frames already taken are finished and yielded, the streams are
     synchronised, and the exception then propagates; the object can run again."""
 
     def __init__(self, model, h, w, depth=2, static_bg=None, occlusion=False, thresh=15.0, promote="numpy1", out="u8",
-                 graph=True, reuse_bg_tower=True, new_bg=None):
+                 graph=True, reuse_bg_tower=True, new_bg=None, flow="given", flow_options=None):
         if not isinstance(model, UNetSimple):
             raise TypeError("ClipStream: the video model is a UNetSimple, got %s" % type(model).__name__)
         if model.dtype not in (torch.bfloat16, torch.float32):
@@ -89,6 +99,19 @@ class ClipStream(SlotPipeline):
         thresh = float(thresh)
         if not thresh >= 0.0:
             raise ValueError("ClipStream: thresh must be a non-negative number, got %r" % (thresh,))
+        if flow not in FLOW_MODES:
+            raise ValueError("ClipStream: flow must be one of %s, got %r" % (FLOW_MODES, flow))
+        self.estimate = flow == "estimate"
+        if flow_options is not None and not self.estimate:
+            raise ValueError("ClipStream: flow_options go with flow='estimate'")
+        opts = dict(ops.FLOW_DEFAULTS)
+        for k, v in dict(flow_options or {}).items():
+            if k not in opts:
+                raise ValueError("ClipStream: flow_options takes %s, got %r" % (sorted(opts), k))
+            opts[k] = v
+        if self.estimate:
+            self.flow_options = dict(zip(("levels", "warps", "iters", "alpha"),
+                                         ops.check_flow_options("ClipStream", h, w, **opts)))
         static_bg = check_static_bg("ClipStream", static_bg, h, w)
         self.new_bg = check_new_bg("ClipStream", out, new_bg, h, w)
         self.model, self.h, self.w, self.depth = model, h, w, depth
@@ -98,6 +121,7 @@ class ClipStream(SlotPipeline):
         self.device = model.device
         self.stats = {"bg_tower_evals": 0, "frames": 0}
         self._plate = self._new_plate = self._buf = None
+        self._cmp0 = self._bw = self._fw = None
 
     # ------------------------------------------------------------------ checks (host only)
     def check_item(self, item):
@@ -108,13 +132,16 @@ class ClipStream(SlotPipeline):
             raise ValueError("ClipStream: the source yields (cmp, bg, backward, forward%s) per frame" %
                              (", new_bg" if per_frame else ""))
         cmp, bg, bw, fw = item[:4]
+        if self.estimate and (bw is not None or fw is not None):
+            raise ValueError("ClipStream: flow='estimate' takes (cmp, bg, None, None%s): both flows are estimated" %
+                             (", new_bg" if per_frame else ""))
         if (bg is None) != (self.static_bg is not None):
             raise ValueError("ClipStream: bg is None exactly when a static_bg was given")
-        if (fw is None) == self.occlusion:
+        if (fw is None) == self.occlusion and not self.estimate:
             raise ValueError("ClipStream: forward is None exactly when occlusion=False")
         for name, a, dt, c in (("cmp", cmp, np.uint8, 3), ("bg", bg, np.uint8, 3), ("backward", bw, np.float32, 2),
                                ("forward", fw, np.float32, 2)) + ((("new_bg", item[4], np.uint8, 3),) if per_frame else ()):
-            if a is None and name in ("bg", "forward"):
+            if a is None and (name in ("bg", "forward") or self.estimate and name == "backward"):
                 continue
             if not isinstance(a, np.ndarray):
                 raise TypeError("ClipStream: %s must be a numpy array, got %s" % (name, type(a).__name__))
@@ -152,6 +179,16 @@ class ClipStream(SlotPipeline):
             self._plate = torch.from_numpy(self.static_bg).to(dev)
         if isinstance(self.new_bg, np.ndarray):
             self._new_plate = torch.from_numpy(self.new_bg).to(dev)
+        if self.estimate:
+            # one set of flow buffers for every slot (the chains run one after another on the compute stream), and
+            # the two pyramids at fixed addresses: every slot's graph reads the previous frame's and leaves its own there
+            o = self.flow_options
+            f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+            self._bw, self._fw = f32(1, self.h, self.w, 2), f32(1, self.h, self.w, 2) if self.occlusion else None
+            self._pyr_cur, self._pyr_prev = (f32(ops.flow_pyramid_floats(self.h, self.w, o["levels"])) for _ in range(2))
+            self._flow_work = torch.zeros(ops.flow_workspace_bytes(self.h, self.w, o["levels"]), dtype=torch.uint8,
+                                          device=dev)
+            self._d_cmp0 = torch.zeros((self.h, self.w, 3), dtype=torch.uint8, device=dev)
         self._slots = [_Slot(self) for _ in range(self.depth)]
         torch.cuda.synchronize(dev)  # the plate and the zeroed buffers, before another stream touches them
         if self.graph:
@@ -170,6 +207,9 @@ class ClipStream(SlotPipeline):
         super()._begin()
         with torch.cuda.stream(self._compute):
             self._alpha.copy_(torch.from_numpy(self._alpha0).view(1, self.h, self.w, 1))
+            if self._cmp0 is not None:  # the previous frame of the first one
+                self._d_cmp0.copy_(torch.from_numpy(self._cmp0))
+                self._pyramid(self._d_cmp0, self._pyr_prev)
 
     def _download(self, s):
         """The slot's result from the model's output buffer (and, composed, the slot's uint8 inputs), which it only
@@ -177,11 +217,28 @@ class ClipStream(SlotPipeline):
         s.download(self._alpha, s.d_cmp, self._plate if self._plate is not None else s.d_bg,
                    self._new_plate if self._new_plate is not None else s.d_nw)
 
+    def _pyramid(self, frame, out):
+        ops.flow_pyramid(frame, self.flow_options["levels"], out=out, work=self._flow_work)
+
+    def _estimate(self, s):
+        """This frame's pyramid, its flows against the previous frame's, and this frame's pyramid left as the
+        previous one for the next chain."""
+        o = self.flow_options
+        self._pyramid(s.d_cmp[0], self._pyr_cur)
+        for out, a, b in ((self._bw, self._pyr_cur, self._pyr_prev), (self._fw, self._pyr_prev, self._pyr_cur)):
+            if out is not None:
+                ops.flow_from_pyramids(a, b, self.h, self.w, o["levels"], o["warps"], o["iters"], o["alpha"], out=out[0],
+                                       work=self._flow_work)
+        self._pyr_prev.copy_(self._pyr_cur)
+
     def _feed(self, s):
         if s.flag is not None:
             s.flag.zero_()
         towers, cat = self._views
-        ops.clip_feed(s.d_cmp, self._plate if self._plate is not None else s.d_bg, self._alpha, s.d_bw, s.d_fw,
+        if self.estimate:
+            self._estimate(s)
+        bw, fw = (self._bw, self._fw) if self.estimate else (s.d_bw, s.d_fw)
+        ops.clip_feed(s.d_cmp, self._plate if self._plate is not None else s.d_bg, self._alpha, bw, fw,
                       self.thresh, self.promote, towers=towers, cat=cat, err=s.flag)
 
     def _submit(self, s, index, cmp, bg, bw, fw, nw=None):
@@ -196,6 +253,8 @@ class ClipStream(SlotPipeline):
         self.stats["bg_tower_evals"] += 1 in towers
         with torch.cuda.stream(self._compute):
             self._compute.wait_event(s.uploaded)
+            if self.estimate and index == 0 and self._cmp0 is None:  # alpha0 belongs to this frame: zero flows
+                self._pyramid(s.d_cmp[0], self._pyr_prev)
             if self.graph:
                 s.graphs[towers].replay()
             else:
@@ -211,9 +270,13 @@ class ClipStream(SlotPipeline):
                              "(the reference's numpy IndexError, flow.py:46)" % s.index)
         return s.h_out[0].numpy().copy()
 
-    def run(self, source, alpha0):
+    def run(self, source, alpha0, cmp0=None):
         """Generator: one [h,w] matte (numpy, the ``out`` dtype), or one composed [h,w,3 | 4] uint8 array, per source
-        item, in source order."""
+        item, in source order.  ``cmp0`` (flow="estimate" only): the uint8 [h,w,3] frame ``alpha0`` belongs to."""
+        if cmp0 is not None and not self.estimate:
+            raise ValueError("ClipStream: cmp0 goes with flow='estimate'")
         self._alpha0 = self.check_alpha0(alpha0)
+        cmp0 = check_static_bg("ClipStream", cmp0, self.h, self.w, name="cmp0")
+        self._cmp0 = None if cmp0 is None else cmp0.copy()
         self.stats = {"bg_tower_evals": 0, "frames": 0}
         yield from super().run(source)

@@ -40,6 +40,26 @@ def warp_bgr(img, flow):
     return out.cpu().numpy()
 
 
+def estimate_flow(cur, prev, levels=6, warps=3, iters=20, alpha=15.0):
+    """The dense flow f between two uint8 [H,W,3] BGR frames with cur(x, y) ~ prev(x + f[...,0], y + f[...,1]), f32
+    [H,W,2] in reader.read_flow layout: what ``warp_img(img_of_prev, f)`` and ``correct_alpha`` take as the backward
+    flow of ``cur``; the forward flow is ``estimate_flow(prev, cur)``.  The reference reads such flows from .flo
+    files and computes none; this is coarse-to-fine Horn-Schunck with warping (ops.estimate_flow).  numpy frames
+    return numpy, device tensors stay on the device."""
+    if isinstance(cur, torch.Tensor) != isinstance(prev, torch.Tensor):
+        raise TypeError("estimate_flow: cur and prev are both numpy arrays or both torch tensors")
+    if isinstance(cur, torch.Tensor):
+        return ops.estimate_flow(cur.contiguous(), prev.contiguous(), levels, warps, iters, alpha)
+    c, p = (np.ascontiguousarray(a) for a in (cur, prev))
+    if c.dtype != np.uint8 or p.dtype != np.uint8:
+        raise TypeError("estimate_flow: uint8 frames expected, got %s and %s" % (c.dtype, p.dtype))
+    if c.ndim != 3 or c.shape[2] != 3 or p.shape != c.shape:
+        raise ValueError("estimate_flow: two [H,W,3] BGR frames of one size expected, got %s and %s" % (c.shape, p.shape))
+    ops.check_flow_options("estimate_flow", c.shape[0], c.shape[1], levels, warps, iters, alpha)
+    out = ops.estimate_flow(torch.from_numpy(c).cuda(), torch.from_numpy(p).cuda(), levels, warps, iters, alpha)
+    return out.cpu().numpy()
+
+
 def correct_alpha(backward, forward, alpha, promote="numpy1", thresh=15.0):
     """flow.correct_alpha (flow.py:36-65): zero alpha where the forward/backward round trip misses by > 15 px.
 

@@ -1058,6 +1058,108 @@ def clip_feed(cmp, bg, prev_alpha, backward, forward=None, thresh=15.0, promote=
     return warped
 
 
+# ---------------------------------------------------------------- optical flow between two decoded frames
+
+FLOW_DEFAULTS = {"levels": 6, "warps": 3, "iters": 20, "alpha": 15.0}
+
+
+def check_flow_options(who, h, w, levels=6, warps=3, iters=20, alpha=15.0):
+    """The estimator's shape and options as vm_flow_estimate checks them, on the host -> (levels, warps, iters,
+    alpha)."""
+    for name, v in (("levels", levels), ("warps", warps), ("iters", iters)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError("%s: %s must be an integer, got %r" % (who, name, v))
+        if v < 1:
+            raise ValueError("%s: %s must be at least 1, got %d" % (who, name, v))
+    alpha = float(alpha)
+    if not alpha > 0.0:
+        raise ValueError("%s: alpha must be a positive number, got %r" % (who, alpha))
+    if h < 16 or w < 16:
+        raise ValueError("%s: frames of at least 16 x 16, got %d x %d" % (who, h, w))
+    return int(levels), int(warps), int(iters), alpha
+
+
+def _check_flow_frame(who, name, t, shape=None):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
+    if t.dtype != torch.uint8:
+        raise TypeError("%s: %s must be uint8, got %s" % (who, name, t.dtype))
+    if t.dim() != 3 or t.shape[2] != 3 or (shape is not None and tuple(t.shape) != shape):
+        raise ValueError("%s: %s must be [h,w,3] BGR%s, got %s" % (who, name, "" if shape is None else " = %s" % (shape,),
+                                                                  tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+    return tuple(t.shape)
+
+
+def _flow_buffer(who, name, t, numel, dtype, device):
+    """A caller's contiguous device buffer of at least ``numel`` elements, or a new one."""
+    if t is None:
+        return torch.empty(numel, dtype=dtype, device=device)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() < numel or not t.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous %s tensor of at least %d elements" % (who, name, dtype, numel))
+    _require_gpu(t)
+    return t
+
+
+def flow_workspace_bytes(h, w, levels=6):
+    return lib().vm_flow_estimate_workspace_bytes(h, w, levels)
+
+
+def flow_pyramid_floats(h, w, levels=6):
+    return lib().vm_flow_pyramid_bytes(h, w, levels) // 4
+
+
+def flow_pyramid(frame, levels=6, out=None, work=None):
+    """vm_flow_pyramid: the smoothed grey pyramid of one uint8 [h,w,3] BGR frame -> f32 [flow_pyramid_floats(h, w,
+    levels)], the levels finest first, each level's start padded to 4 floats."""
+    h, w, _ = _check_flow_frame("flow_pyramid", "frame", frame)
+    levels = check_flow_options("flow_pyramid", h, w, levels)[0]
+    _require_gpu(frame)
+    out = _flow_buffer("flow_pyramid", "out", out, flow_pyramid_floats(h, w, levels), torch.float32, frame.device)
+    work = _flow_buffer("flow_pyramid", "work", work, flow_workspace_bytes(h, w, levels), torch.uint8, frame.device)
+    check(lib().vm_flow_pyramid(_ptr(frame), h, w, levels, _ptr(out), _ptr(work), stream_handle()), "flow_pyramid")
+    return out
+
+
+def flow_from_pyramids(cur, prev, h, w, levels=6, warps=3, iters=20, alpha=15.0, out=None, work=None):
+    """vm_flow_from_pyramids: the flow of estimate_flow from two flow_pyramid results of [h,w] frames."""
+    levels, warps, iters, alpha = check_flow_options("flow_from_pyramids", h, w, levels, warps, iters, alpha)
+    for t in (cur, prev):
+        _require_gpu(t)
+    n = flow_pyramid_floats(h, w, levels)
+    cur = _flow_buffer("flow_from_pyramids", "cur", cur, n, torch.float32, cur.device)
+    prev = _flow_buffer("flow_from_pyramids", "prev", prev, n, torch.float32, cur.device)
+    if out is not None and tuple(out.shape) != (h, w, 2):
+        raise ValueError("flow_from_pyramids: out must be [h,w,2] = %s, got %s" % ((h, w, 2), tuple(out.shape)))
+    out = _flow_buffer("flow_from_pyramids", "out", out, h * w * 2, torch.float32, cur.device)
+    work = _flow_buffer("flow_from_pyramids", "work", work, flow_workspace_bytes(h, w, levels), torch.uint8, cur.device)
+    check(lib().vm_flow_from_pyramids(_ptr(cur), _ptr(prev), h, w, levels, warps, iters, alpha, _ptr(out), _ptr(work),
+                                      stream_handle()), "flow_from_pyramids")
+    return out.view(h, w, 2)
+
+
+def estimate_flow(cur_u8, prev_u8, levels=6, warps=3, iters=20, alpha=15.0, out=None, work=None):
+    """vm_flow_estimate: the dense flow f between two uint8 [h,w,3] BGR frames with cur(x, y) ~ prev(x + f[...,0],
+    y + f[...,1]) -> f32 [h,w,2] in reader.read_flow layout: the backward flow warp_img / clip_feed consume (the
+    forward flow is estimate_flow(prev, cur)).  Coarse-to-fine Horn-Schunck with warping, f32 (include/vmatting.h).
+    ``out``: a contiguous f32 [h,w,2] device tensor; ``work``: a uint8 device buffer of flow_workspace_bytes(h, w,
+    levels); both are allocated when None."""
+    shape = _check_flow_frame("estimate_flow", "cur", cur_u8)
+    _check_flow_frame("estimate_flow", "prev", prev_u8, shape)
+    h, w, _ = shape
+    levels, warps, iters, alpha = check_flow_options("estimate_flow", h, w, levels, warps, iters, alpha)
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (h, w, 2)):
+        raise ValueError("estimate_flow: out must be [h,w,2] = %s, got %s" % ((h, w, 2), tuple(getattr(out, "shape", ()))))
+    _require_gpu(cur_u8)
+    _require_gpu(prev_u8)
+    out = _flow_buffer("estimate_flow", "out", out, h * w * 2, torch.float32, cur_u8.device)
+    work = _flow_buffer("estimate_flow", "work", work, flow_workspace_bytes(h, w, levels), torch.uint8, cur_u8.device)
+    check(lib().vm_flow_estimate(_ptr(cur_u8), _ptr(prev_u8), h, w, levels, warps, iters, alpha, _ptr(out), _ptr(work),
+                                 stream_handle()), "estimate_flow")
+    return out.view(h, w, 2)
+
+
 # ---------------------------------------------------------------- training step (train.py:288-343, config 5)
 
 def matting_loss_backward(pred, gt, raw_fg, in_bg, in_cmp, out=None):
