@@ -98,6 +98,9 @@ const char* vm_last_error(void);
  *                    through the output tiles for folded upconvs only (default), 1 = always, 2 = never
  *   "rows_kernel", "rows_min_blocks", "rows_min_cin", "rows_up"  row-stationary kernel dispatch (1, 400, 128, 0)
  *   "border_ks"      folded-upconv border pass granule split: 1 (default), 2 or 4
+ *   "border_fuse"    the border pass in extra blocks of the folded kernel's own launch instead of a launch of its
+ *                    own: 0 = off, 1 = in the streaming folded kernel, 2 = in the persistent one too (default;
+ *                    bit-identical; split-K, the split-fp16 form and the row-stationary kernel keep the separate pass)
  *   The patch / row-stationary / persistent / strip choices and "up_skip" are bit-identical (every output keeps its
  *   MFMA sequence); "conv_kernel", "head_kernel" and "softmax_kernel" pick kernels with another f32 summation order
  *   (within the stated tolerances). */
@@ -106,6 +109,9 @@ int vm_set_option(const char* key, long value);
  * rocprofv3 reports it (e.g. "vm::conv3x3_mfma<unsigned short, 128, 128>"); "" before the first call.
  * Used to attribute per-kernel profiler counters (bench.py); no reference counterpart. */
 const char* vm_conv3x3_last_kernel(void);
+/* 1 if the calling thread's last vm_conv3x3_up2x*_nhwc ran its border pass inside the folded kernel's launch
+ * ("border_fuse"), 0 if it launched the border kernel.  For tests and profiles; no reference counterpart. */
+int vm_conv3x3_last_border_fused(void);
 
 /* ---------------------------------------------------------------- 3x3 convolution
  * Replaces tf.nn.conv2d(x, w, [1,1,1,1], 'SAME') + tf.nn.bias_add + the activation /

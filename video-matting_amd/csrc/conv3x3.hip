@@ -715,6 +715,7 @@ static const OptDef conv_options[] = {
 #endif
     {"pair_xin_wide", &g_opt.pair_xin_wide, OPT_RANGE, 2, {0, 1}},
     {"border_ks", &g_opt.border_ks, OPT_SET, 3, {1, 2, 4}},
+    {"border_fuse", &g_opt.border_fuse, OPT_RANGE, 2, {0, 2}},
     {"patch_repi", &g_opt.patch_repi, OPT_RANGE, 2, {0, 1}},
     {"persist_rounds", &g_opt.persist_rounds, OPT_RANGE, 2, {0, 64}, " (0: any grid)"},
     {"persist_up_rounds", &g_opt.persist_up_rounds, OPT_RANGE, 2, {0, 64}, " (0: any grid)"},

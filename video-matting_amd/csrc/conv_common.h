@@ -78,6 +78,13 @@ struct ConvArgs {
   // split-fp16 input stored as two slabs [l, h] of xalias channels (K = 3 * xalias: [l, h, h]): input channels
   // [2 * xalias, 3 * xalias) are read from [xalias, 2 * xalias) (src_chan), so h is stored once
   int xalias;
+  // folded upconv with its border pass in the same launch (vm_set_option "border_fuse"; conv_border.h): the caller
+  // sets bwant (1 = the streaming folded kernel may, 2 = the persistent one too), the plain packed filter bw / bK_pad
+  // and the frame count; a launcher that takes it sets bfuse = 1 and adds bblocks border blocks to its grid (the
+  // streaming kernel's first blocks, the persistent kernel's last), whose tile blocks then leave the frame's outer
+  // ring (output row 0 / 2H-1, column 0 / 2W-1) unwritten
+  int bwant, bfuse, bblocks, bframes, bK_pad;
+  const void* bw;
 };
 
 // compile-time loop: f(std::integral_constant<int, I>) for I in [I, N)
@@ -204,6 +211,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t w_rsrc(const ConvArgs& a, int 
   const uint32_t bytes = (uint32_t)((long)(a.cout_pad - n0) * a.K_pad * (long)sizeof(T));
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(Wb), 0, bytes, 0x00020000);
 }
+
+// folded upconv with the border pass in its launch (ConvArgs::bfuse): the low-res row / column whose phase-(a, b)
+// outputs lie on the full-res frame's outer ring (output row 0 for a = 0, row 2H-1 for a = 1; likewise columns), which
+// the tile blocks leave to the border blocks; -1 (no row / column) otherwise.  Wave-uniform.
+__device__ __forceinline__ int ring_row(const ConvArgs& a, int phase) { return !a.bfuse ? -1 : (phase >> 1) ? a.H - 1 : 0; }
+__device__ __forceinline__ int ring_col(const ConvArgs& a, int phase) { return !a.bfuse ? -1 : (phase & 1) ? a.W - 1 : 0; }
 
 constexpr int OOB = (int)0x80000000;
 // the same for the issue-bound strip pair kernel: the bit pattern of -4.0f, an inline constant, so a select of it needs

@@ -40,6 +40,10 @@ struct ConvOptions {
   long conv_prio = 0;  // ConvArgs::prio for the 8-wave conv kernels (patch, persistent patch, row-stationary)
 
   long border_ks = 1;  // folded-upconv border pass: granule split (1, 2 or 4 wave groups per block)
+  // the border pass inside the folded kernel's own launch (ConvArgs::bfuse): 0 = a launch of its own, 1 = the
+  // streaming folded kernel takes it (as its first blocks), 2 = the persistent one too (as the blocks after its
+  // walkers).  Same-box A/B of the 1080p forward against the separate pass: 1 = +0.4 %, 2 = +1.4..1.7 %
+  long border_fuse = 2;
   long up_skip_mask = 3;  // folded upconvs: which zero taps are skipped (1 = kernel row, 2 = column, 3 = both)
   long patch_repi = 1;  // patch kernel: register epilogue (bf16 outputs, no packed frames) where the tiling allows
   // channel-banded patch tiles (ConvArgs::cband): 0 off, 1 folded upconvs, 2 all.  Off: measured on upconv_2 (9.4 MB

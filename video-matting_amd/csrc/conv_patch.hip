@@ -2,6 +2,7 @@
 // the streaming kernel conv3x3_patch with its FIRST (conv1_1 fused in), folded-upconv and split-K forms, the persistent
 // row-slot kernel conv3x3_patch_persist, the split-K reduction, and their routing (dispatch_patch), which also reaches
 // the row-stationary kernel of conv_rows.hip.
+#include "conv_border.h"
 #include "conv_dispatch.h"
 
 namespace vm {
@@ -41,6 +42,9 @@ struct PatchCfg {
   static constexpr bool REMAP = TPM == 32 && TW == 32 && WM % 2 == 0 && TH == WM;
   static constexpr bool REPI_OK = G == 3 && (REMAP || TPM == 64);
   static constexpr int PSTEP = REMAP ? 1 : 2;  // pixel fragment of the row below fragment fp (pool partner)
+  // folded upconvs: the border pass can run in extra blocks of the launch (ConvArgs::bfuse), one 4-wave group per 256
+  // threads, each staging in its own slice of the main pipeline's LDS
+  static constexpr bool BFUSE_OK = REPI_OK && NT % 256 == 0 && MAIN >= NT / 256 * BORDER_LDS;
   __device__ static int prow(int wm, int fp) { return REMAP ? 2 * (wm >> 1) + fp : (wm * TPM + fp * 16) / TW; }
   __device__ static int pcol(int wm, int fp) { return REMAP ? 16 * (wm & 1) : (wm * TPM + fp * 16) % TW; }
   __device__ static int tpix(int wm, int fp) { return prow(wm, fp) * TW + pcol(wm, fp); }  // first tile pixel
@@ -140,6 +144,27 @@ void conv3x3_patch(ConvArgs a) {
   using T = uint16_t;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NW = C::NW, NT = C::NT, FP = C::FP, FC = C::FC, XPW = C::XPW, WPW = C::WPW;
+  // the folded upconv's border pass in this launch (ConvArgs::bfuse): the first a.bblocks blocks run it and leave, the
+  // rest are the tiles.  First, not last: beside the conv's blocks a border block's latency chain takes about two
+  // tile times, which a greedy fill absorbs when it starts with the launch and which sticks out of the launch's end
+  // when it starts with the last round of tiles (measured)
+  constexpr bool BFUSE = UPSKIP && !FIRST && std::is_same<MT, uint16_t>::value && C::BFUSE_OK;
+  [[maybe_unused]] int bid = 0;  // BFUSE: the tile block index
+  if constexpr (BFUSE) {
+    bid = (int)blockIdx.x;
+    if (a.bfuse) {
+      if (__builtin_expect(bid < a.bblocks, 0)) {  // (out of line: the tile path keeps its code layout)
+        up2x_border_fused<NT>(a, smem, bid);
+        return;
+      }
+      bid -= a.bblocks;
+    }
+  }
+  // (the other instantiations read blockIdx.x as ever: their code is unchanged)
+  auto bx = [&]() -> unsigned {
+    if constexpr (BFUSE) return (unsigned)bid;
+    else return blockIdx.x;
+  };
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -150,16 +175,16 @@ void conv3x3_patch(ConvArgs a) {
   const int th = (H + C::TH - 1) / C::TH, tw = (VW + C::TW - 1) / C::TW;
   int st, nt;
   if (a.cband) {  // channel-banded: XCD b % 8 owns output tiles [xcd * cband, +cband) over every pixel tile
-    const int i = blockIdx.x >> 3;
+    const int i = bx() >> 3;
     st = i / a.cband;
-    nt = (blockIdx.x & 7) * a.cband + (i - st * a.cband);
+    nt = (bx() & 7) * a.cband + (i - st * a.cband);
   } else if (a.ngroup) {  // grouped: ngroup output tiles x every pixel tile, group after group (XCD ranges within)
-    const int t = xcd_tile(blockIdx.x, a.tiles_total);
+    const int t = xcd_tile(bx(), a.tiles_total);
     const int per = (a.tiles_total / a.tiles_n) * a.ngroup, gi = t / per, r = t - gi * per;
     st = r / a.ngroup;
     nt = gi * a.ngroup + (r - st * a.ngroup);
   } else {
-    const int t = xcd_tile(blockIdx.x, a.tiles_total);
+    const int t = xcd_tile(bx(), a.tiles_total);
     st = t / a.tiles_n;
     nt = t - st * a.tiles_n;
   }
@@ -652,6 +677,7 @@ void conv3x3_patch(ConvArgs a) {
         const int chb = n0 + wn * C::TPN + g2 * 32;  // first block channel of this 32-channel group
         const int phase = a.up ? chb / a.up_cout : 0;
         const int cb = chb - phase * a.up_cout;
+        const int rex = ring_row(a, phase), cex = ring_col(a, phase);
         float v[FP][2][4];
 #pragma unroll
         for (int fp = 0; fp < FP; ++fp) {
@@ -671,7 +697,9 @@ void conv3x3_patch(ConvArgs a) {
           hb[fp][g2] = make_uint4(pk[0].x, pk[0].y, pk[1].x, pk[1].y);
           const uint4 d = chunk_pair(pk[0], pk[1]);
           const int tr = C::prow(wm, fp), tc = C::pcol(wm, fp) + col;
-          const bool ok = r0 + tr < H && c0 + tc < W && cb + c16 * 8 < ccap && !a.y_skip;
+          bool ok = r0 + tr < H && c0 + tc < W && cb + c16 * 8 < ccap && !a.y_skip;
+          // (fused border pass: the ring belongs to the border blocks; the store is issued all the same)
+          if constexpr (BFUSE) ok = ok && r0 + tr != rex && c0 + tc != cex;
           const int pix = a.up ? (2 * tr + (phase >> 1)) * YW + 2 * tc + (phase & 1) : tr * W + tc;
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, d),
                                                  yrs, ok ? pix * ycs2 + (cb + c16 * 8) * 2 : OOB, 0, 0);
@@ -720,13 +748,16 @@ void conv3x3_patch(ConvArgs a) {
                                  bf16x2_bits(hwv[kk][6], hwv[kk][7]));
           const int phase = a.up ? (n0 + wn * C::TPN) / a.up_cout : 0;
           const int YH = a.up ? 2 * H : H;
+          const int hrex = ring_row(a, phase), hcex = ring_col(a, phase);
 #pragma unroll
           for (int fp = 0; fp < FP; ++fp) {
             f32x4 d = f32x4{0.f, 0.f, 0.f, 0.f};
             mma16<T>(hwf[0], hb[fp][0], d);
             mma16<T>(hwf[1], hb[fp][1], d);
             const int tr = C::prow(wm, fp), tc = C::pcol(wm, fp) + col;
-            if (ckq < 3 && r0 + tr < H && c0 + tc < W) {
+            bool hok = ckq < 3 && r0 + tr < H && c0 + tc < W;
+            if constexpr (BFUSE) hok = hok && r0 + tr != hrex && c0 + tc != hcex;  // (fused border pass: not the ring)
+            if (hok) {
               const int yy = a.up ? 2 * (r0 + tr) + (phase >> 1) : r0 + tr;
               const int xx = a.up ? 2 * (c0 + tc) + (phase & 1) : c0 + tc;
               *reinterpret_cast<f32x4*>(a.hd + (((long)n * YH + yy) * YW + xx) * 12 + 4 * ckq) = d;
@@ -869,8 +900,18 @@ void conv3x3_patch_persist(ConvArgs a) {
   const int wm = wave;
   const int H = a.H, W = a.W, cs = a.x_cstride;
   const int th = (H + C::TH - 1) / C::TH, tw = (W + C::TW - 1) / C::TW;
+  // the folded upconv's border pass in this launch (ConvArgs::bfuse): the a.bblocks blocks past the walkers run it
+  constexpr bool BFUSE = UPSKIP && C::BFUSE_OK;
+  if constexpr (BFUSE) {
+    const int nwalk = (int)gridDim.x - a.bblocks;
+    if (__builtin_expect((int)blockIdx.x >= nwalk, 0)) {  // (out of line: the walkers keep their code layout)
+      up2x_border_fused<NT>(a, smem, (int)blockIdx.x - nwalk);
+      return;
+    }
+  }
   const int tn = a.tiles_n, sp = a.tiles_total / tn, CT = tn * BN;
-  const int xcd = blockIdx.x & 7, jw = blockIdx.x >> 3, J = (int)(gridDim.x >> 3);
+  const int xcd = blockIdx.x & 7, jw = blockIdx.x >> 3,
+            J = BFUSE ? ((int)gridDim.x - a.bblocks) >> 3 : (int)(gridDim.x >> 3);
   const int lo = (int)((long)xcd * sp / 8), hi = (int)((long)(xcd + 1) * sp / 8);
   const int nitem = (hi - lo) * tn;
   int it = 0, q = jw;
@@ -1047,6 +1088,7 @@ void conv3x3_patch_persist(ConvArgs a) {
       const int chb = n0 + g2 * 32;
       const int phase = a.up ? chb / a.up_cout : 0;
       const int cb = chb - phase * a.up_cout;
+      const int rex = ring_row(a, phase), cex = ring_col(a, phase);
       float v[FP][2][4];
 #pragma unroll
       for (int f = 0; f < 2; ++f) {
@@ -1076,7 +1118,9 @@ void conv3x3_patch_persist(ConvArgs a) {
                    make_uint4(pk[0].x, pk[0].y, pk[1].x, pk[1].y), dh[fp]);
         const uint4 d = chunk_pair(pk[0], pk[1]);
         const int tr = C::prow(wm, fp), tc = C::pcol(wm, fp) + col;
-        const bool ok = r0 + tr < H && c0 + tc < W && cb + c16 * 8 < ccap && !a.y_skip;
+        bool ok = r0 + tr < H && c0 + tc < W && cb + c16 * 8 < ccap && !a.y_skip;
+        // (fused border pass: the ring belongs to the border blocks; the store is issued, and counted, all the same)
+        if constexpr (BFUSE) ok = ok && r0 + tr != rex && c0 + tc != cex;
         const int pix = a.up ? (2 * tr + (phase >> 1)) * YW + 2 * tc + (phase & 1) : tr * W + tc;
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, d), yrs,
                                                ok ? pix * ycs2 + (cb + c16 * 8) * 2 : OOB, 0, 0);
@@ -1115,11 +1159,14 @@ void conv3x3_patch_persist(ConvArgs a) {
     if (a.hd) {
       const int phase = a.up ? n0 / a.up_cout : 0;
       const int YH = a.up ? 2 * H : H;
+      const int hrex = ring_row(a, phase), hcex = ring_col(a, phase);
 #pragma unroll
       for (int fp = 0; fp < FP; ++fp) {
         const f32x4 d = dh[fp];
         const int tr = C::prow(wm, fp), tc = C::pcol(wm, fp) + col;
-        if (ckq < 3 && r0 + tr < H && c0 + tc < W) {
+        bool hok = ckq < 3 && r0 + tr < H && c0 + tc < W;
+        if constexpr (BFUSE) hok = hok && r0 + tr != hrex && c0 + tc != hcex;  // (fused border pass: not the ring)
+        if (hok) {  // (uncounted stores: waiting longer is safe)
           const int yy = a.up ? 2 * (r0 + tr) + (phase >> 1) : r0 + tr;
           const int xx = a.up ? 2 * (c0 + tc) + (phase & 1) : c0 + tc;
           *reinterpret_cast<f32x4*>(a.hd + (((long)n * YH + yy) * YW + xx) * 12 + 4 * ckq) = d;
@@ -1251,6 +1298,20 @@ int launch_splitk_reduce(const ConvArgs& a, hipStream_t st) {
 }
 
 // ================================================================ launchers and routing
+// the border blocks a folded kernel of nt threads adds to its grid (ConvArgs::bfuse): one 4-wave group per 16
+// border pixels x 64 output channels, nt / 256 groups per block; left off where the grid would not fit
+static void plan_border_fuse(ConvArgs& a, int nt) {
+  a.bfuse = a.bblocks = 0;
+  // (the border blocks address the low-res frame with 32-bit element offsets)
+  if (!a.up || !a.bw || a.up_cout % 64 || (long)a.H * a.W * a.x_cstride + a.cin_pad > 0x7fffffffL) return;
+  const long nb = 4L * a.W + 2 * (2L * a.H - 2);
+  const long groups = (a.bframes * nb + 15) / 16 * (a.up_cout / 64), per = nt / 256;
+  const long blocks = (groups + per - 1) / per;
+  if (blocks <= 0 || a.tiles_total + blocks > 0x7fffffffL) return;
+  a.bfuse = 1;
+  a.bblocks = (int)blocks;
+}
+
 template <int BN, int WM, int WN, int S, int TH = 8, int MINB = 1, int UNR = 9, bool PF = false, int ABL = 0,
           bool FIRST = false, int G = 1, bool UPSKIP = false>
 static int launch_patch(ConvArgs& a, hipStream_t st) {
@@ -1275,6 +1336,7 @@ static int launch_patch(ConvArgs& a, hipStream_t st) {
   const long sp = a.vstride ? ((a.H + C::TH - 1) / C::TH) * (long)((a.vW + C::TW - 1) / C::TW)
                             : N * ((a.H + C::TH - 1) / C::TH) * ((a.W + C::TW - 1) / C::TW);
   a.tiles_n = (a.cout + BN - 1) / BN;
+  a.bfuse = a.bblocks = 0;
   a.repi = (int)g_opt.patch_repi;
   a.upmask = (int)g_opt.up_skip_mask;
   a.prio = (int)g_opt.conv_prio;
@@ -1290,7 +1352,10 @@ static int launch_patch(ConvArgs& a, hipStream_t st) {
   snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_patch<%d, %d, %d, %d, %d, %d, %d, %s, %d, %s, %d, %s%s>",
            BN, WM, WN, S, TH, MINB, UNR, PF ? "true" : "false", ABL, FIRST ? "true" : "false", G,
            UPSKIP ? "true" : "false", f16 ? ", vm::f16_t" : "");
-  const dim3 grid(a.tiles_total, a.ksplit > 1 ? a.ksplit : 1);
+  if constexpr (UPSKIP && !FIRST && C::BFUSE_OK) {
+    if (a.bwant >= 1 && !f16 && a.repi && !a.vstride && a.ksplit <= 1 && a.y_dtype == VM_BF16) plan_border_fuse(a, C::NT);
+  }
+  const dim3 grid(a.tiles_total + a.bblocks, a.ksplit > 1 ? a.ksplit : 1);
   if constexpr (F16_OK) {
     if (f16) {
       hipLaunchKernelGGL((conv3x3_patch<BN, WM, WN, S, TH, MINB, UNR, PF, ABL, FIRST, G, UPSKIP, f16_t>), grid,
@@ -1363,8 +1428,11 @@ static int launch_patch_persist(ConvArgs& a, hipStream_t st) {
   const long J = resident / 8;  // walkers per XCD band (every band has >= 2 rounds of items)
   snprintf(g_last_kernel, sizeof g_last_kernel, "vm::conv3x3_patch_persist<%d, %d, %d, %d, %d, %d, %s>", BN, WM, WN, S,
            TH, MINB, UPSKIP ? "true" : "false");
-  hipLaunchKernelGGL((conv3x3_patch_persist<BN, WM, WN, S, TH, MINB, UPSKIP>), dim3((unsigned)(8 * J)), dim3(C::NT), lds,
-                     st, a);
+  if constexpr (UPSKIP && C::BFUSE_OK) {
+    if (a.bwant >= 2) plan_border_fuse(a, C::NT);
+  }
+  hipLaunchKernelGGL((conv3x3_patch_persist<BN, WM, WN, S, TH, MINB, UPSKIP>), dim3((unsigned)(8 * J + a.bblocks)),
+                     dim3(C::NT), lds, st, a);
   return check_launch("conv3x3_patch_persist");
 }
 

@@ -82,6 +82,7 @@ SIGNATURES = [
     ("vm_last_error", ctypes.c_char_p, []),
     ("vm_set_option", c_int, [ctypes.c_char_p, c_long]),
     ("vm_conv3x3_last_kernel", ctypes.c_char_p, []),
+    ("vm_conv3x3_last_border_fused", c_int, []),
     ("vm_conv3x3_packed_bytes", c_size_t, [c_int, c_int, c_int]),
     ("vm_conv3x3_pack_weights", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("vm_conv3x3_nhwc", c_int, [P, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, P, c_void_p]),
@@ -246,6 +247,11 @@ def set_option(key, value):
 def last_conv_kernel():
     """vm_conv3x3_last_kernel: rocprofv3 spelling of the kernel the last conv call launched."""
     return lib().vm_conv3x3_last_kernel().decode()
+
+
+def last_border_fused():
+    """vm_conv3x3_last_border_fused: whether the last folded upconv ran its border pass inside its own launch."""
+    return bool(lib().vm_conv3x3_last_border_fused())
 
 
 # torch's private C getters behind torch.cuda.current_stream(d).cuda_stream, looked up once; if a torch release
