@@ -298,3 +298,41 @@ def test_f16x3_fused_head_matches_two_chunk_head(vgg0):
     (a0, l0), (a1, l1) = outs
     assert np.abs(l0 - l1).max() <= 1e-6 * np.abs(l1).max()
     assert np.abs(a0 - a1).max() <= 2e-5
+
+
+# the 19 profiled convs of one split forward at 1x35x61 in walk order (the head runs unprofiled): scope, the rows and
+# columns of its input (no level of 35x61 is an exact 2x: every pool is ragged), its concat width, cout
+PROFILE_WALK = (("conv1_1", 35, 61, None, 64), ("conv1_2", 35, 61, 64, 64), ("conv2_1", 18, 31, 64, 128),
+                ("conv2_2", 18, 31, 128, 128), ("conv3_1", 9, 16, 128, 256), ("conv3_2", 9, 16, 256, 256),
+                ("conv3_3", 9, 16, 256, 256), ("conv4_1", 5, 8, 256, 512), ("conv4_2", 5, 8, 512, 512),
+                ("conv4_3", 5, 8, 512, 512), ("conv5_1", 3, 4, 512, 512), ("conv5_2", 3, 4, 512, 512),
+                ("upconv_1", 5, 8, 512, 512), ("conv4_4", 5, 8, 1024, 512), ("upconv_2", 9, 16, 512, 256),
+                ("conv3_4", 9, 16, 512, 256), ("upconv_3", 18, 31, 256, 128), ("conv2_3", 18, 31, 256, 128),
+                ("upconv_4", 35, 61, 128, 64))
+
+
+# (slabs the conv reads per input channel, conv1_1's slab width: f16x3's first_slab 32, bf16x6's 16)
+@pytest.mark.parametrize("dtype,slabs,first", [("f16x3", 3, 32), ("bf16x6", 6, 16)])
+def test_split_forward_profile_lists_the_walk(dtype, slabs, first, vgg0):
+    """conv_profile over one split forward: one (flops, kernel, ev0, ev1, (n, h, w, cin, cout)) entry per conv, in
+    the walk's order, cin = the slabs read x the concat width."""
+    from vmatting import ops, unet
+    np.random.seed(0)
+    m = unet.UNetVideo(vgg0, dtype=dtype).prepare()
+    x = torch.from_numpy((np.random.RandomState(1).normal(size=(1, 35, 61, 7)) * 0.5).astype(np.float32)).to(DEV)
+    try:
+        prof = ops.conv_profile(True)
+        assert ops._CONV_PROFILE is prof
+        m.forward(x)
+        torch.cuda.synchronize()
+    finally:
+        ops.conv_profile(False)
+    assert ops._CONV_PROFILE is None
+    want = [(1, h, w, slabs * (first if cw is None else cw), co) for _, h, w, cw, co in PROFILE_WALK]
+    assert [len(p) for p in prof] == [5] * 19
+    assert [p[4] for p in prof] == want
+    for (flops, kernel, ev0, ev1, _), (n, h, w, ci, co) in zip(prof, want):
+        assert flops == 2 * n * h * w * 9 * ci * co
+        assert isinstance(kernel, str) and kernel
+        assert ev0.elapsed_time(ev1) >= 0.0
+    assert m.split_mode == dtype and not m.overflowed()

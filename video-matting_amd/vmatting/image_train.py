@@ -29,13 +29,10 @@ import torch
 
 from . import ops, parallel
 from .train import TrainerBase, TrainGraphBase, _to_device_f32
-from .unet import UNetImage, _levels
+from .unet import CONVS, UNetImage, _levels
 
 # build order of unet.py:96-143 (the TF variable creation order): scope, keeps a bias
-LAYERS = (("conv1_1", True), ("conv1_2", True), ("conv2_1", True), ("conv2_2", True), ("conv3_1", True),
-          ("conv3_2", True), ("conv3_3", True), ("conv4_1", True), ("conv4_2", True), ("conv4_3", True),
-          ("conv5_1", True), ("conv5_2", True), ("upconv_1", False), ("conv4_4", True), ("upconv_2", False),
-          ("conv3_4", True), ("upconv_3", False), ("conv2_3", True), ("upconv_4", False), ("conv1_5", True))
+LAYERS = tuple((s, keeps_bias) for s, _, _, _, _, keeps_bias in CONVS)
 
 
 def param_layout(shapes):

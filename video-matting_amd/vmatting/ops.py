@@ -45,6 +45,11 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _ref(v):
+    """byref of a vm_tensor, or NULL for an absent one."""
+    return None if v is None else ctypes.byref(v)
+
+
 def _f32(t):
     if t is None:
         return None
@@ -209,11 +214,7 @@ def conv3x3(x, pc, act="none", out=None, out_dtype=None, affine=None, pool_out=N
         yv = nhwc(out)
         wsz = lib().vm_conv3x3_workspace_bytes(ctypes.byref(xv), pc.cin, pc.cout) if splitk else 0
         ws = _workspace(wsz, x.device) if wsz else None
-        prof = _CONV_PROFILE
-        if prof is not None:
-            ev0 = torch.cuda.Event(enable_timing=True)
-            ev1 = torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        prof = _ConvProf()
         rc = lib().vm_conv3x3_ex_nhwc(ctypes.byref(xv), nsrc, stride, _ptr(pc.packed), pc.cin, pc.cout,
                                       _ptr(pc.bias), _ptr(scale), _ptr(shift), _lib.ACT[act], ctypes.byref(yv),
                                       _ptr(ws), wsz, stream_handle())
@@ -225,17 +226,10 @@ def conv3x3(x, pc, act="none", out=None, out_dtype=None, affine=None, pool_out=N
                                           _ptr(scale), _ptr(shift), _lib.ACT[act], ctypes.byref(yv), _ptr(ws), wsz,
                                           stream_handle())
         check(rc, "conv3x3")
-        if prof is not None:
-            ev1.record()
-            prof.append((2 * n * h * w * 9 * pc.cin * pc.cout, _lib.last_conv_kernel(), ev0, ev1,
-                         (n, h, w, pc.cin, pc.cout)))
+        prof.done(2 * n * h * w * 9 * pc.cin * pc.cout, (n, h, w, pc.cin, pc.cout))
         return out
     xv, yv = nhwc(x), nhwc(out)
-    prof = _CONV_PROFILE
-    if prof is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    prof = _ConvProf()
     fused = False
     if pool_out is not None:
         pv = nhwc(pool_out)
@@ -248,10 +242,7 @@ def conv3x3(x, pc, act="none", out=None, out_dtype=None, affine=None, pool_out=N
     if not fused:
         check(lib().vm_conv3x3_nhwc(ctypes.byref(xv), _ptr(pc.packed), pc.cin, pc.cout, _ptr(pc.bias), _ptr(scale),
                                     _ptr(shift), _lib.ACT[act], ctypes.byref(yv), stream_handle()), "conv3x3")
-    if prof is not None:
-        ev1.record()
-        prof.append((2 * n * h * w * 9 * pc.cin * pc.cout, _lib.last_conv_kernel(), ev0, ev1,
-                     (n, h, w, pc.cin, pc.cout)))
+    prof.done(2 * n * h * w * 9 * pc.cin * pc.cout, (n, h, w, pc.cin, pc.cout))
     if pool_out is not None and not fused:
         maxpool2x2(out, out=pool_out)
     return out
@@ -272,11 +263,7 @@ def conv_head(x, pc, act="none", out=None, alpha=None, partial=None):
         if alpha.dtype != torch.float32 or not alpha.is_contiguous() or alpha.numel() != n * h * w:
             raise ValueError("alpha must be a contiguous f32 tensor of n*h*w elements")
     xv, yv = nhwc(x), nhwc(out)
-    prof = _CONV_PROFILE
-    if prof is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    prof = _ConvProf()
     if partial is not None:  # + the per-tap shares of the channels x does not carry (conv_pair_first_head)
         if partial.dtype != torch.float32 or not partial.is_contiguous() or tuple(partial.shape) != (n, h, w, 12):
             raise ValueError("partial must be a contiguous f32 [n,h,w,12] tensor")
@@ -287,9 +274,7 @@ def conv_head(x, pc, act="none", out=None, alpha=None, partial=None):
         check(lib().vm_conv3x3_head_nhwc(ctypes.byref(xv), _ptr(pc.packed), pc.cin, _ptr(pc.bias), _ptr(pc.scale),
                                          _ptr(pc.shift), _lib.ACT[act], ctypes.byref(yv), _ptr(alpha),
                                          stream_handle()), "conv3x3_head")
-    if prof is not None:
-        ev1.record()
-        prof.append((2 * n * h * w * 9 * pc.cin, _lib.last_conv_kernel(), ev0, ev1))
+    prof.done(2 * n * h * w * 9 * pc.cin)
     return out
 
 
@@ -314,22 +299,15 @@ def conv_pair_first_head(x, pc1, pc2, head_w, head_coff, partial, act2="relu", o
         out = torch.empty((n, h, w, pc2.cout), dtype=torch.bfloat16, device=x.device)
     xv, yv = nhwc(x), nhwc(out)
     pv = nhwc(pool_out) if pool_out is not None else None
-    prof = _CONV_PROFILE
-    if prof is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    prof = _ConvProf()
     rc = lib().vm_conv3x3_pair_first_head_nhwc(
         ctypes.byref(xv), _ptr(pc1.packed), pc1.cin, _ptr(pc1.bias), _ptr(pc2.packed), pc2.cout, _ptr(pc2.bias),
         _ptr(pc2.scale), _ptr(pc2.shift), _lib.ACT[act2], ctypes.byref(yv),
-        ctypes.byref(pv) if pv is not None else None, _ptr(head_w), int(head_w.shape[2]), head_coff, _ptr(partial),
-        int(bool(store_y)), stream_handle())
+        _ref(pv), _ptr(head_w), int(head_w.shape[2]), head_coff, _ptr(partial), int(bool(store_y)), stream_handle())
     if rc == _lib.VM_EUNSUPPORTED and fallback:
         return None  # e.g. a kernel-selection override (vm_set_option "conv_kernel"/"pair_kernel") rules it out
     check(rc, "conv3x3_pair_first_head")
-    if prof is not None:
-        ev1.record()
-        prof.append((2 * n * h * w * 9 * (pc1.cin * pc1.cout + pc2.cin * pc2.cout), _lib.last_conv_kernel(), ev0, ev1))
+    prof.done(2 * n * h * w * 9 * (pc1.cin * pc1.cout + pc2.cin * pc2.cout))
     return out
 
 
@@ -345,11 +323,7 @@ def conv_pair_first(x, pc1, pc2, act2="relu", out=None, pool_out=None, mid=None,
             and pc2.cin == 64:
         xv, yv = nhwc(x), nhwc(out)
         pv = nhwc(pool_out) if pool_out is not None else None
-        prof = _CONV_PROFILE
-        if prof is not None:
-            ev0 = torch.cuda.Event(enable_timing=True)
-            ev1 = torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        prof = _ConvProf()
         if keep_mid:
             if mid is None or mid.dtype != torch.bfloat16:
                 raise ValueError("keep_mid needs a bf16 mid buffer")
@@ -357,19 +331,15 @@ def conv_pair_first(x, pc1, pc2, act2="relu", out=None, pool_out=None, mid=None,
             rc = lib().vm_conv3x3_pair_first_mid_nhwc(ctypes.byref(xv), _ptr(pc1.packed), pc1.cin, _ptr(pc1.bias),
                                                       _ptr(pc2.packed), pc2.cout, _ptr(pc2.bias), _ptr(pc2.scale),
                                                       _ptr(pc2.shift), _lib.ACT[act2], ctypes.byref(yv),
-                                                      ctypes.byref(pv) if pv is not None else None, ctypes.byref(mv),
-                                                      stream_handle())
+                                                      _ref(pv), ctypes.byref(mv), stream_handle())
         else:
             rc = lib().vm_conv3x3_pair_first_nhwc(ctypes.byref(xv), _ptr(pc1.packed), pc1.cin, _ptr(pc1.bias),
                                                   _ptr(pc2.packed), pc2.cout, _ptr(pc2.bias), _ptr(pc2.scale),
                                                   _ptr(pc2.shift), _lib.ACT[act2], ctypes.byref(yv),
-                                                  ctypes.byref(pv) if pv is not None else None, stream_handle())
+                                                  _ref(pv), stream_handle())
         if rc != _lib.VM_EUNSUPPORTED:
             check(rc, "conv3x3_pair_first")
-            if prof is not None:
-                ev1.record()
-                prof.append((2 * n * h * w * 9 * (pc1.cin * pc1.cout + pc2.cin * pc2.cout), _lib.last_conv_kernel(),
-                             ev0, ev1))
+            prof.done(2 * n * h * w * 9 * (pc1.cin * pc1.cout + pc2.cin * pc2.cout))
             return out
     if x.dtype != pc1.dtype:  # the unfused path takes the frame in the compute dtype, channels padded to 8
         c = x.shape[-1]
@@ -392,19 +362,13 @@ def upconv3x3(x, pc, act="none", out=None, size=None, rbuf=None, fold=True):
     up = pc.up2x() if fold and (oh, ow) == (2 * h, 2 * w) and x.dtype == pc.dtype else None
     if up is not None:
         xv, yv = nhwc(x), nhwc(out)
-        prof = _CONV_PROFILE
-        if prof is not None:
-            ev0 = torch.cuda.Event(enable_timing=True)
-            ev1 = torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        prof = _ConvProf()
         rc = lib().vm_conv3x3_up2x_nhwc(ctypes.byref(xv), _ptr(up), _ptr(pc.packed), pc.cin, pc.cout, _ptr(pc.bias),
                                         _ptr(pc.scale), _ptr(pc.shift), _lib.ACT[act], ctypes.byref(yv),
                                         stream_handle())
         if rc != _lib.VM_EUNSUPPORTED:
             check(rc, "conv3x3_up2x")
-            if prof is not None:
-                ev1.record()
-                prof.append((2 * n * oh * ow * 9 * pc.cin * pc.cout, _lib.last_conv_kernel(), ev0, ev1))
+            prof.done(2 * n * oh * ow * 9 * pc.cin * pc.cout)
             return out
     r = resize_bilinear(x, (oh, ow), out=rbuf)
     return conv3x3(r, pc, act, out=out)
@@ -429,11 +393,7 @@ def upconv3x3_head(x, pc, head_w, head_coff, partial, act="none", out=None, stor
     if out is None:
         out = torch.empty((n, 2 * h, 2 * w, pc.cout), dtype=x.dtype, device=x.device)
     xv, yv = nhwc(x), nhwc(out)
-    prof = _CONV_PROFILE
-    if prof is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    prof = _ConvProf()
     rc = lib().vm_conv3x3_up2x_head_nhwc(
         ctypes.byref(xv), _ptr(up), _ptr(pc.packed), pc.cin, pc.cout, _ptr(pc.bias), _ptr(pc.scale), _ptr(pc.shift),
         _lib.ACT[act], ctypes.byref(yv), _ptr(head_w), int(head_w.shape[2]), head_coff, _ptr(partial),
@@ -441,9 +401,7 @@ def upconv3x3_head(x, pc, head_w, head_coff, partial, act="none", out=None, stor
     if rc == _lib.VM_EUNSUPPORTED:
         return None
     check(rc, "conv3x3_up2x_head")
-    if prof is not None:
-        ev1.record()
-        prof.append((2 * n * 4 * h * w * 9 * pc.cin * pc.cout, _lib.last_conv_kernel(), ev0, ev1))
+    prof.done(2 * n * 4 * h * w * 9 * pc.cin * pc.cout)
     return out
 
 
@@ -461,22 +419,34 @@ def head_from_partials(pa, pb, bias=None, logits=None, alpha=None):
     lv = nhwc(logits)
     if alpha is not None and (alpha.dtype != torch.float32 or not alpha.is_contiguous() or alpha.numel() != n * h * w):
         raise ValueError("alpha must be a contiguous f32 tensor of n*h*w values")
-    prof = _CONV_PROFILE
-    if prof is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    prof = _ConvProf()
     check(lib().vm_conv3x3_head_from_partials(_ptr(pa), _ptr(pb), n, h, w, _ptr(bias), ctypes.byref(lv),
                                               _ptr(alpha), stream_handle()), "head_from_partials")
-    if prof is not None:  # (the head's own conv FLOPs were made in the two epilogues; listed for its time)
-        ev1.record()
-        prof.append((2 * n * h * w * 9 * 128, _lib.last_conv_kernel(), ev0, ev1))
+    prof.done(2 * n * h * w * 9 * 128)  # (its conv FLOPs were made in the two epilogues; listed for its time)
     return logits
 
 
-# When a list, conv3x3 appends (algorithmic FLOPs, is_head, start_event, end_event) per launch —
-# HIP events on the launch stream, used by bench.py for the roofline's achieved TFLOP/s.
+# When a list, every conv launch appends (algorithmic FLOPs, kernel name, start_event, end_event[, (n, h, w, cin,
+# cout)]) — HIP events on the launch stream, used by bench.py for the roofline's achieved TFLOP/s.
 _CONV_PROFILE = None
+
+
+class _ConvProf:
+    """One conv launch's profile entry: create it right before the launch (records the start event when profiling is
+    on), call ``done`` after a launch that ran (a fall-back after VM_EUNSUPPORTED appends nothing)."""
+
+    def __init__(self):
+        self.prof = _CONV_PROFILE
+        if self.prof is not None:
+            self.ev0 = torch.cuda.Event(enable_timing=True)
+            self.ev1 = torch.cuda.Event(enable_timing=True)
+            self.ev0.record()
+
+    def done(self, flops, shape=None):
+        if self.prof is not None:
+            self.ev1.record()
+            entry = (flops, _lib.last_conv_kernel(), self.ev0, self.ev1)
+            self.prof.append(entry if shape is None else entry + (shape,))
 
 
 def conv_profile(enable):
@@ -1180,10 +1150,9 @@ def bn_backward(x, dy, y, mean, var, gamma, eps=1e-3, dx=None, dgamma=None, dbet
     dbias: the gradient of a conv bias added before the BN (= channel sum of dx) from the same reduction."""
     c = dy.shape[-1]
     views = [None if t is None else nhwc(t) for t in (x, dy, y, dx, dx2)]
-    ref = lambda v: None if v is None else ctypes.byref(v)  # noqa: E731
     ws = _workspace(lib().vm_bn_backward_workspace_bytes(c), dy.device)
-    check(lib().vm_bn_backward_ex_nhwc(ref(views[0]), ref(views[1]), ref(views[2]), _ptr(mean), _ptr(var),
-                                       _ptr(gamma), float(eps), ref(views[3]), ref(views[4]), _ptr(dgamma),
+    check(lib().vm_bn_backward_ex_nhwc(_ref(views[0]), _ref(views[1]), _ref(views[2]), _ptr(mean), _ptr(var),
+                                       _ptr(gamma), float(eps), _ref(views[3]), _ref(views[4]), _ptr(dgamma),
                                        _ptr(dbeta), _ptr(dbias), _ptr(ws), stream_handle()), "bn_backward")
     return dx
 
@@ -1192,10 +1161,9 @@ def bn_backward_apply(x, dy, y, mean, var, gamma, sum_g, sum_gx, count, dx, eps=
     """The input-gradient pass of bn_backward with given channel sums over ``count`` pixels (SyncBN: the sums
     all-reduced over the replicas, count = their pixels)."""
     views = [None if t is None else nhwc(t) for t in (x, dy, y, dx, dx2)]
-    ref = lambda v: None if v is None else ctypes.byref(v)  # noqa: E731
-    check(lib().vm_bn_backward_apply_nhwc(ref(views[0]), ref(views[1]), ref(views[2]), _ptr(mean), _ptr(var),
+    check(lib().vm_bn_backward_apply_nhwc(_ref(views[0]), _ref(views[1]), _ref(views[2]), _ptr(mean), _ptr(var),
                                           _ptr(gamma), float(eps), _ptr(_f32(sum_g)), _ptr(_f32(sum_gx)), int(count),
-                                          ref(views[3]), ref(views[4]), stream_handle()), "bn_backward_apply")
+                                          _ref(views[3]), _ref(views[4]), stream_handle()), "bn_backward_apply")
     return dx
 
 
@@ -1229,10 +1197,9 @@ def relu_backward_bias(dy, y, dz, dbias, add=None):
     when dy has the 2x2 SAME pool's shape — add + the max-pool adjoint of dy (TF MaxPoolGrad's first maximum)."""
     _f32(dbias)
     views = [nhwc(dy), nhwc(y), None if add is None else nhwc(add), nhwc(dz)]
-    ref = lambda v: None if v is None else ctypes.byref(v)  # noqa: E731
     ws = _workspace(lib().vm_relu_backward_bias_workspace_bytes(y.shape[-1]), y.device)
-    check(lib().vm_relu_backward_bias_nhwc(ref(views[0]), ref(views[1]), ref(views[2]), ref(views[3]), _ptr(dbias),
-                                           _ptr(ws), stream_handle()), "relu_backward_bias")
+    check(lib().vm_relu_backward_bias_nhwc(_ref(views[0]), _ref(views[1]), _ref(views[2]), _ref(views[3]),
+                                           _ptr(dbias), _ptr(ws), stream_handle()), "relu_backward_bias")
     return dz
 
 

@@ -36,17 +36,16 @@ import numpy as np
 import torch
 
 from . import ops
+from .split6 import SplitForward
+from .unet import split_layers
 
 # slab order of the activations and the filter parts they meet: l*Wh, h*Wl, h*Wh
 W_PARTS = (0, 1, 0)  # index into (Wh, Wl)
 WTOP = 12  # filter scale: max |W * 2^t| in (2^11, 2^12]
 
-# (conv scope, channels of its split input (the concat width), output channels)
-LAYERS = (("conv1_1", 8, 64), ("conv1_2", 64, 64), ("conv2_1", 64, 128), ("conv2_2", 128, 128),
-          ("conv3_1", 128, 256), ("conv3_2", 256, 256), ("conv3_3", 256, 256), ("conv4_1", 256, 512),
-          ("conv4_2", 512, 512), ("conv4_3", 512, 512), ("conv5_1", 512, 512), ("conv5_2", 512, 512),
-          ("upconv_1", 512, 512), ("conv4_4", 1024, 512), ("upconv_2", 512, 256), ("conv3_4", 512, 256),
-          ("upconv_3", 256, 128), ("conv2_3", 256, 128), ("upconv_4", 128, 64), ("conv1_5", 128, 1))
+# (conv scope, channels of its split input (the concat width), output channels); conv1_1's 8 live channels are packed
+# at Split3Forward.first_slab
+LAYERS = split_layers(8, 1)
 
 
 def filter_scale(w):
@@ -108,8 +107,7 @@ def split3h(x, y, pool=None, slab=0, overflow=None):
     device int32) is set to 1 where |x| >= 65520."""
     xv, yv = ops.nhwc(x), ops.nhwc(y)
     pv = ops.nhwc(pool) if pool is not None else None
-    ref = (lambda v: None if v is None else ops.ctypes.byref(v))
-    ops.check(ops.lib().vm_split3h_nhwc(ref(xv), ref(yv), ref(pv), int(slab), ops._ptr(overflow),
+    ops.check(ops.lib().vm_split3h_nhwc(ops._ref(xv), ops._ref(yv), ops._ref(pv), int(slab), ops._ptr(overflow),
                                         ops.stream_handle()), "split3h")
     return y
 
@@ -123,35 +121,18 @@ def resize_split3h(x, y, slab=0, overflow=None):
     return y
 
 
-def _prof_begin():
-    prof = ops._CONV_PROFILE
-    if prof is None:
-        return None
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    return prof, ev0, ev1
-
-
-def _prof_end(p, x, pc):
-    if p is not None:
-        prof, ev0, ev1 = p
-        ev1.record()
-        n, h, w, _ = x.shape
-        prof.append((2 * n * h * w * 9 * pc.cin * pc.cout, ops._lib.last_conv_kernel(), ev0, ev1,
-                     (n, h, w, pc.cin, pc.cout)))
-
-
 def conv_f32(x, pc, y, act="relu", splitk=True):
     """The fp16 conv of split input x (a two-slab [l, h] view read as [l, h, h], or a plain fp16 view of pc.cin
     channels) into the f32 view y (vm_conv3x3_ex_nhwc; split-K on small grids)."""
     xv, yv = ops.nhwc(x), ops.nhwc(y)
     wsz = ops.lib().vm_conv3x3_workspace_bytes(ops.ctypes.byref(xv), pc.cin, pc.cout) if splitk else 0
     ws = ops._workspace(wsz, x.device) if wsz else None
-    p = _prof_begin()
+    prof = ops._ConvProf()
     ops.check(ops.lib().vm_conv3x3_ex_nhwc(ops.ctypes.byref(xv), 1, 0, ops._ptr(pc.packed), pc.cin, pc.cout,
                                            ops._ptr(pc.bias), ops._ptr(pc.scale), ops._ptr(pc.shift), ops._lib.ACT[act],
                                            ops.ctypes.byref(yv), ops._ptr(ws), wsz, ops.stream_handle()), "conv3x3(f16)")
-    _prof_end(p, x, pc)
+    n, h, w, _ = x.shape
+    prof.done(2 * n * h * w * 9 * pc.cin * pc.cout, (n, h, w, pc.cin, pc.cout))
     return y
 
 
@@ -162,13 +143,13 @@ def conv_split(x, pc, y, act="relu", pool=None, overflow=None, y_slab=0, pool_sl
     pv = ops.nhwc(pool) if pool is not None else None
     wsz = ops.lib().vm_conv3x3_workspace_bytes(ops.ctypes.byref(xv), pc.cin, pc.cout) if (splitk and pool is None) else 0
     ws = ops._workspace(wsz, x.device) if wsz else None
-    ref = (lambda v: None if v is None else ops.ctypes.byref(v))
-    p = _prof_begin()
+    prof = ops._ConvProf()
     ops.check(ops.lib().vm_conv3x3_split3_nhwc(
-        ref(xv), ops._ptr(pc.packed), pc.cin, pc.cout, ops._ptr(pc.bias), ops._ptr(pc.scale), ops._ptr(pc.shift),
-        ops._lib.ACT[act], ref(yv), int(y_slab), ref(pv), int(pool_slab), ops._ptr(overflow), ops._ptr(ws), wsz,
-        ops.stream_handle()), "conv3x3_split3")
-    _prof_end(p, x, pc)
+        ops._ref(xv), ops._ptr(pc.packed), pc.cin, pc.cout, ops._ptr(pc.bias), ops._ptr(pc.scale), ops._ptr(pc.shift),
+        ops._lib.ACT[act], ops._ref(yv), int(y_slab), ops._ref(pv), int(pool_slab), ops._ptr(overflow), ops._ptr(ws),
+        wsz, ops.stream_handle()), "conv3x3_split3")
+    n, h, w, _ = x.shape
+    prof.done(2 * n * h * w * 9 * pc.cin * pc.cout, (n, h, w, pc.cin, pc.cout))
     return y
 
 
@@ -176,33 +157,28 @@ def up_split(x, pc_up, pc, y, overflow=None, act="none", y_slab=0):
     """vm_conv3x3_up2x_split3_nhwc: the folded 2x upconv of the low-res split input x ([l, h]) into the full-res split
     view y (pc_up: the folded filter's parts, pc: the plain filter's, for the border pass; same scale)."""
     xv, yv = ops.nhwc(x), ops.nhwc(y)
-    p = _prof_begin()
+    prof = ops._ConvProf()
     ops.check(ops.lib().vm_conv3x3_up2x_split3_nhwc(
         ops.ctypes.byref(xv), ops._ptr(pc_up.packed), ops._ptr(pc.packed), pc.cin, pc.cout, ops._ptr(pc.bias),
         ops._ptr(pc.scale), ops._ptr(pc.shift), ops._lib.ACT[act], ops.ctypes.byref(yv), int(y_slab),
         ops._ptr(overflow), ops.stream_handle()), "conv3x3_up2x_split3")
-    if p is not None:  # FLOPs of the unfolded conv it stands for (its output pixels)
-        prof, ev0, ev1 = p
-        ev1.record()
-        n, h, w, _ = y.shape
-        prof.append((2 * n * h * w * 9 * pc.cin * pc.cout, ops._lib.last_conv_kernel(), ev0, ev1,
-                     (n, h, w, pc.cin, pc.cout)))
+    n, h, w, _ = y.shape  # FLOPs of the unfolded conv it stands for (its output pixels)
+    prof.done(2 * n * h * w * 9 * pc.cin * pc.cout, (n, h, w, pc.cin, pc.cout))
     return y
 
 
-def whole(buf):
-    """The split-layout view of all channels of a 2*S-wide split buffer [l, h]."""
-    return buf[..., :buf.shape[-1] // 2]
+def _descale(cout, t, bias=None):
+    """A conv's epilogue (acc * 2^-t) + b: exact descale, then the bias (unet.py:41,73)."""
+    return dict(scale=np.full(cout, 1.0 / t, np.float32), shift=np.zeros(cout, np.float32) if bias is None else bias)
 
 
-def seg(buf, off, c):
-    """Channels [off, off + c) of a 2*S-wide split buffer (the writers put the slabs at p*S + off)."""
-    return buf[..., off:off + c]
-
-
-class Split3Forward:
+class Split3Forward(SplitForward):
     """The split-fp16 x3 forward of a UNet (unet.UNetVideo / UNetImage) with its parameters."""
 
+    SLABS, DTYPE, LAYERS = 2, torch.float16, LAYERS  # (two stored slabs [l, h], read as [l, h, h])
+    # + the folded upconvs' low-res split inputs: conv4_4 / conv3_4 / conv2_3 written split
+    SPLIT = dict(SplitForward.SPLIT, c44s=(3, 512), c34s=(2, 256), c23s=(1, 128))
+    LOWRES = {"conv4_4": "c44s", "conv3_4": "c34s", "conv2_3": "c23s"}
     # conv -> split in the conv's epilogue (vm_conv3x3_split3_nhwc); False: f32 output + vm_split3h_nhwc (A/B)
     fuse_split = True
     # the exact-2x upconvs on the folded filter (fuse_split only) — measured slower here (1080p: upconv_2 / _3 / _4
@@ -218,80 +194,35 @@ class Split3Forward:
     head_fused = True
 
     def __init__(self, model):
-        self.m = model
-        self.dev = model.device
-        self.convs = {}
         self.scales = {}
-        self.up = {}  # folded upconv filters (FOLD)
-        for name, cin, cout in LAYERS:
-            w, b = model.params[name]
-            t = filter_scale(w)
-            self.scales[name] = t
-            if name == "conv1_5":
-                wf = split3_filter(w, cin, 1, t)
-                if self.head_fused:  # [l, h, h] x [Wh, Wl, Wh], descaled + bias in the epilogue
-                    self.head = [ops.PackedConv(wf, None, "f16", self.dev, scale=np.full(1, 1.0 / t, np.float32),
-                                                shift=np.zeros(1, np.float32) if b is None else b)]
-                    self.convs[name] = self.head[0]
-                    continue
-                # [l | h] against [Wh | Wl] (256 channels), then [h] against [Wh] adding the first chunk's logits
-                self.head = [ops.PackedConv(wf[:, :, :256].contiguous(), None, "f16", self.dev),
-                             ops.PackedConv(wf[:, :, 256:].contiguous(), None, "f16", self.dev,
-                                            scale=np.full(1, 1.0 / t, np.float32),
-                                            shift=np.zeros(1, np.float32) if b is None else b)]
-                self.convs[name] = self.head[1]
-                continue
-            cp = cin
-            if name == "conv1_1":
-                cp = self.first_slab  # slab width (7 or 6 live channels): see first_slab
-            if name in FOLD:  # one scale for the folded filter and the plain one (its border pass)
-                wu = fold_up2x(w)
-                t = min(t, filter_scale(wu))  # max |W' * 2^t| and max |W * 2^t| both <= 2^12
-                self.scales[name] = t
-                self.up[name] = ops.PackedConv(split3_filter(wu, cin, 4 * cout, t), None, "f16", self.dev,
-                                               scale=np.full(cout, 1.0 / t, np.float32),
-                                               shift=np.zeros(cout, np.float32))
-            wf = split3_filter(w, cp, cout, t)
-            if name == "conv1_1" and cp == 8:
-                wf = torch.cat([wf, torch.zeros((3, 3, 8, cout))], 2)
-            # epilogue (acc * 2^-t) + b: exact descale, then the bias (unet.py:41,73)
-            self.convs[name] = ops.PackedConv(wf, None, "f16", self.dev, scale=np.full(cout, 1.0 / t, np.float32),
-                                              shift=np.zeros(cout, np.float32) if b is None else b)
+        super().__init__(model)  # (.up: the folded upconv filters, FOLD)
         self.overflow = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self._b, self._key = None, None
-        self.logits = None
+        self._ovf = self.overflow  # the flag slot of the forward under way
 
-    def weights_flat(self):
-        out = []
-        for pc in [self.convs[k] for k in sorted(self.convs) if k != "conv1_5"] + self.head + [self.up[k] for k in
-                                                                                             sorted(self.up)]:
-            out.append(pc.packed)
-            for t in (pc.bias, pc.scale, pc.shift):
-                if t is not None:
-                    out.append(t)
-        return out
+    def pack(self, name, cin, cout, w, b):
+        t = self.scales[name] = filter_scale(w)
+        if name == "conv1_5":
+            wf = split3_filter(w, cin, 1, t)
+            if self.head_fused:  # [l, h, h] x [Wh, Wl, Wh], descaled + bias in the epilogue
+                self.head = [ops.PackedConv(wf, None, "f16", self.dev, **_descale(1, t, b))]
+            else:  # [l | h] against [Wh | Wl] (256 channels), then [h] against [Wh] adding the first chunk's logits
+                self.head = [ops.PackedConv(wf[:, :, :256].contiguous(), None, "f16", self.dev),
+                             ops.PackedConv(wf[:, :, 256:].contiguous(), None, "f16", self.dev, **_descale(1, t, b))]
+            return self.head[-1]
+        cp = self.first_slab if name == "conv1_1" else cin  # slab width (7 or 6 live channels): see first_slab
+        if name in FOLD:  # one scale for the folded filter and the plain one (its border pass)
+            wu = fold_up2x(w)
+            t = self.scales[name] = min(t, filter_scale(wu))  # max |W' * 2^t| and max |W * 2^t| both <= 2^12
+            self.up[name] = ops.PackedConv(split3_filter(wu, cin, 4 * cout, t), None, "f16", self.dev,
+                                           **_descale(cout, t))
+        wf = split3_filter(w, cp, cout, t)
+        if name == "conv1_1" and cp == 8:
+            wf = torch.cat([wf, torch.zeros((3, 3, 8, cout))], 2)
+        return ops.PackedConv(wf, None, "f16", self.dev, **_descale(cout, t, b))
 
-    def _buffers(self, n, h, w):
-        if self._key == (n, h, w):
-            return self._b
-        from .unet import _levels
-        L = _levels(h, w)
-        dev = self.dev
-        S = lambda lv, c: torch.empty((n, L[lv][0], L[lv][1], 2 * c), dtype=torch.float16, device=dev)  # noqa
-        F = lambda lv, c: torch.empty((n, L[lv][0], L[lv][1], c), dtype=torch.float32, device=dev)  # noqa
-        fs = self.first_slab
+    def x_width(self):
         # (slab 8: [l, h, h] + a zero 4th slab in one granule; wider: the two stored slabs [l, h], read as [l, h, h])
-        b = {"x": torch.zeros((n, L[0][0], L[0][1], 32 if fs == 8 else 2 * fs), dtype=torch.float16, device=dev),
-             "s11": S(0, 64), "cat1": S(0, 128), "r4": S(0, 128),
-             "p1": S(1, 64), "s21": S(1, 128), "cat2": S(1, 256), "r3": S(1, 256),
-             "p2": S(2, 128), "s31": S(2, 256), "s32": S(2, 256), "cat3": S(2, 512), "r2": S(2, 512),
-             "p3": S(3, 256), "s41": S(3, 512), "s42": S(3, 512), "cat4": S(3, 1024), "r1": S(3, 512),
-             "p4": S(4, 512), "s51": S(4, 512),
-             "c44s": S(3, 512), "c34s": S(2, 256), "c23s": S(1, 128),  # the folded upconvs' low-res inputs
-             "f0": F(0, 128), "f1": F(1, 256), "f2": F(2, 512), "f3": F(3, 512), "f4": F(4, 512),
-             "lg0": F(0, 1), "out": F(0, 1)}
-        self._b, self._key = b, (n, h, w)
-        return b
+        return 16 if self.first_slab == 8 else self.first_slab
 
     def overflowed(self):
         """True when the last forward that ran on the model's own flag (no ``overflow=`` slot) met |x| >= 65520
@@ -305,75 +236,45 @@ class Split3Forward:
         if overflow is not None and not (isinstance(overflow, torch.Tensor) and overflow.dtype == torch.int32 and
                                          overflow.numel() == 1 and overflow.device == x.device):
             raise ValueError("overflow must be a one-element int32 view on the frames' device")
-        from .unet import _levels
-        n, h, w, c = x.shape
-        b = self._buffers(n, h, w)
-        L = _levels(h, w)
-        C = self.convs
-        ovf = self.overflow if overflow is None else overflow
-        ovf.zero_()
-        fs = self.first_slab
-        # channels 0..7 of each slab (the frame's 7 or 6 and zeros); the rest of the slabs stay zero from allocation
-        split3h(x, b["x"][..., :8], slab=fs, overflow=ovf)
+        self._ovf = self.overflow if overflow is None else overflow
+        self._ovf.zero_()
+        return super().forward(x, out)
 
-        def conv(src, name, dst_f32, act="relu", splitk=True):
-            return conv_f32(src, C[name], dst_f32, act, splitk)
+    def first(self, x, y):
+        split3h(x, y, slab=self.first_slab, overflow=self._ovf)
 
-        def sp(f, y, pool=None):
-            return split3h(f, y, pool, overflow=ovf)
+    def conv(self, src, name, dst_f32, act="relu", splitk=True):
+        return conv_f32(src, self.convs[name], dst_f32, act, splitk)
 
-        def cs(src, name, dst_f32, y, pool=None, act="relu"):
-            """conv -> split (-> pool split): fused, or the f32 round trip"""
-            if self.fuse_split:
-                return conv_split(src, C[name], y, act, pool, ovf)
-            # (no split-K under a pool, as the fused form: the same sums, bit for bit)
-            return sp(conv(src, name, dst_f32, act, splitk=pool is None), y, pool)
+    def conv_split(self, src, name, dst_f32, y, pool, act):
+        """conv -> split (-> pool split): fused, or the f32 round trip"""
+        if self.fuse_split:
+            return conv_split(src, self.convs[name], y, act, pool, self._ovf)
+        # (no split-K under a pool, as the fused form: the same sums, bit for bit)
+        split3h(self.conv(src, name, dst_f32, act, splitk=pool is None), y, pool, overflow=self._ovf)
 
-        def resize_split(f_src, lv, r_split):
-            if self.fuse_split:  # the resize written split, no f32 resized tensor
-                return resize_split3h(f_src, r_split, overflow=ovf)
-            rr = torch.empty((n, L[lv][0], L[lv][1], f_src.shape[-1]), dtype=torch.float32, device=x.device)
-            ops.resize_bilinear(f_src, L[lv], out=rr)
-            sp(rr, r_split)
+    def resize_split(self, f_src, r_split, lv):
+        if self.fuse_split:  # the resize written split, no f32 resized tensor
+            return resize_split3h(f_src, r_split, overflow=self._ovf)
+        rr = torch.empty(r_split.shape[:3] + f_src.shape[3:], dtype=torch.float32, device=f_src.device)
+        ops.resize_bilinear(f_src, rr.shape[1:3], out=rr)
+        split3h(rr, r_split, overflow=self._ovf)
 
-        f0, f1, f2, f3, f4 = b["f0"], b["f1"], b["f2"], b["f3"], b["f4"]
-        # encoder (unet.py:170-189)
-        cs(b["x"], "conv1_1", f0[..., :64], whole(b["s11"]))
-        cs(b["s11"], "conv1_2", f0[..., :64], seg(b["cat1"], 64, 64), pool=whole(b["p1"]))
-        cs(b["p1"], "conv2_1", f1[..., :128], whole(b["s21"]))
-        cs(b["s21"], "conv2_2", f1[..., :128], seg(b["cat2"], 128, 128), pool=whole(b["p2"]))
-        cs(b["p2"], "conv3_1", f2[..., :256], whole(b["s31"]))
-        cs(b["s31"], "conv3_2", f2[..., :256], whole(b["s32"]))
-        cs(b["s32"], "conv3_3", f2[..., :256], seg(b["cat3"], 256, 256), pool=whole(b["p3"]))
-        cs(b["p3"], "conv4_1", f3, whole(b["s41"]))
-        cs(b["s41"], "conv4_2", f3, whole(b["s42"]))
-        cs(b["s42"], "conv4_3", f3, seg(b["cat4"], 512, 512), pool=whole(b["p4"]))
-        cs(b["p4"], "conv5_1", f4, whole(b["s51"]))
-        y52 = conv(b["s51"], "conv5_2", f4)
-        # decoder: resize (f32) -> split -> conv (no bias, no relu) into the concat's up range (unet.py:191-200)
-        resize_split(y52, 3, whole(b["r1"]))
-        cs(b["r1"], "upconv_1", f3, seg(b["cat4"], 0, 512), act="none")
-        fold = self.fold_up and self.fuse_split
+    def level(self, src, name, r, up, y):
+        """As the base's; with fold_up (and fuse_split), where the resize is an exact 2x, conv ``name`` is written split
+        and ``up`` runs as the folded 2x upconv on that low-res output (unet.py:192-200)."""
+        x = self._b[src]
+        if not (self.fold_up and self.fuse_split and up in FOLD and
+                tuple(y.shape[1:3]) == (2 * x.shape[1], 2 * x.shape[2])):
+            return super().level(src, name, r, up, y)
+        s = self._b[self.LOWRES[name]]
+        self.conv_split(x, name, self.f32(name), self.whole(s), None, "relu")
+        up_split(s, self.up[up], self.convs[up], y, self._ovf)
 
-        def level(src_cat, conv_name, f_dst, s_name, lv, r_name, up_name, up_f32, y):
-            """conv (relu) over the concat -> upconv (no bias, no relu) into the next concat's up range: the folded
-            2x upconv on its split low-res output where the resize is an exact 2x, else f32 -> resize -> split ->
-            conv (unet.py:192-200)"""
-            if fold and L[lv] == (2 * L[lv + 1][0], 2 * L[lv + 1][1]):
-                cs(b[src_cat], conv_name, f_dst, whole(b[s_name]))
-                up_split(b[s_name], self.up[up_name], C[up_name], y, ovf)
-            else:
-                f = conv(b[src_cat], conv_name, f_dst)
-                resize_split(f, lv, whole(b[r_name]))
-                cs(b[r_name], up_name, up_f32, y, act="none")
-
-        level("cat4", "conv4_4", f3, "c44s", 2, "r2", "upconv_2", f2[..., :256], seg(b["cat3"], 0, 256))
-        level("cat3", "conv3_4", f2[..., :256], "c34s", 1, "r3", "upconv_3", f1[..., :128], seg(b["cat2"], 0, 128))
-        level("cat2", "conv2_3", f1[..., :128], "c23s", 0, "r4", "upconv_4", f0[..., :64], seg(b["cat1"], 0, 64))
-        # conv1_5 + sigmoid (unet.py:203-205): [l | h] x [Wh | Wl], then [h] x [Wh] + those logits, * 2^-t + bias
-        alpha = b["out"] if out is None else out
-        lg0 = b["lg0"]
-        logits = f0[..., :1]
+    def run_head(self, alpha):
+        """[l | h] x [Wh | Wl], then [h] x [Wh] + those logits, * 2^-t + bias (head_fused: one call)."""
+        b = self._b
+        lg0, logits = b["lg0"], b["f0"][..., :1]
         chunks = (((b["cat1"], logits, None),) if self.head_fused else
                   ((b["cat1"], lg0, None), (b["cat1"][..., 128:], logits, lg0)))
         for k, (xs, yv, acc) in enumerate(chunks):
@@ -383,5 +284,4 @@ class Split3Forward:
                 ops.ctypes.byref(xv), ops._ptr(pc.packed), pc.cin, None, ops._ptr(pc.scale),
                 ops._ptr(pc.shift), ops._ptr(acc), ops.ctypes.byref(yvv),
                 ops._ptr(alpha if k == len(chunks) - 1 else None), ops.stream_handle()), "conv3x3_head_acc_ex")
-        self.logits = logits
-        return alpha
+        return logits

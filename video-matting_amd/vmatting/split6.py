@@ -24,16 +24,14 @@ import numpy as np
 import torch
 
 from . import ops
+from .unet import COUT, LEVEL, _levels, split_layers
 
 # slab order of the activations and of the filter parts they meet (vm_split6_nhwc): l*h, m*m, h*l, m*h, h*m, h*h
 W_PARTS = (0, 1, 2, 0, 1, 0)  # index into (wh, wm, wl)
 
-# (conv scope, input channels of its split input (the concat width), output channels)
-LAYERS = (("conv1_1", 16, 64), ("conv1_2", 64, 64), ("conv2_1", 64, 128), ("conv2_2", 128, 128),
-          ("conv3_1", 128, 256), ("conv3_2", 256, 256), ("conv3_3", 256, 256), ("conv4_1", 256, 512),
-          ("conv4_2", 512, 512), ("conv4_3", 512, 512), ("conv5_1", 512, 512), ("conv5_2", 512, 512),
-          ("upconv_1", 512, 512), ("conv4_4", 1024, 512), ("upconv_2", 512, 256), ("conv3_4", 512, 256),
-          ("upconv_3", 256, 128), ("conv2_3", 256, 128), ("upconv_4", 128, 64), ("conv1_5", 128, 8))
+# (conv scope, input channels of its split input (the concat width), output channels): conv1_1 reads 6 slabs of 16
+# (8 live): 96 channels, whole 32-channel granules for the patch kernel; conv1_5's output is padded to 8
+LAYERS = split_layers(16, 8)
 
 
 def split3(w):
@@ -65,129 +63,163 @@ def split6(x, y, pool=None):
     y's concat width), and optionally the split of its 2x2 SAME max-pool into ``pool``."""
     xv, yv = ops.nhwc(x), ops.nhwc(y)
     pv = ops.nhwc(pool) if pool is not None else None
-    ref = (lambda v: None if v is None else ops.ctypes.byref(v))
-    ops.check(ops.lib().vm_split6_nhwc(ref(xv), ref(yv), ref(pv), ops.stream_handle()), "split6")
+    ops.check(ops.lib().vm_split6_nhwc(ops._ref(xv), ops._ref(yv), ops._ref(pv), ops.stream_handle()), "split6")
     return y
 
 
-def whole(buf):
-    """The split-layout view of all channels of a 6*S-wide split buffer."""
-    return buf[..., :buf.shape[-1] // 6]
+class SplitForward:
+    """unet.py:161-205 over split activations: the walk, the buffer plan and the caches that the bf16x6 and the f16x3
+    (split3.Split3Forward) forwards share.  A subclass gives the split format (SLABS stored slabs of DTYPE per
+    buffer, its LAYERS view of the conv table, ``pack``) and what one step does (``first``, ``conv``, ``conv_split``,
+    ``resize_split``, ``run_head``; optionally another ``level``)."""
 
-
-def seg(buf, off, c):
-    """The split-layout view of channels [off, off + c) of a 6*S-wide split buffer: a [n,h,w,c] view starting at
-    channel off whose rows are 6*S wide (split6 writes the 6 slabs at p*S + off)."""
-    return buf[..., off:off + c]
-
-
-class Split6Forward:
-    """The split-bf16 x6 forward of a UNet (unet.UNetVideo / UNetImage) with its parameters."""
+    # the activation buffers, name -> (pyramid level, channels): split ones (SLABS * channels wide; the concats cat1..4
+    # are [up, skip] channel ranges, r1..r4 the resized upconv inputs, "x" is added by plan) and f32 ones (f0..f4: the
+    # convs' f32 scratch per level)
+    SPLIT = dict(s11=(0, 64), cat1=(0, 128), r4=(0, 128), p1=(1, 64), s21=(1, 128), cat2=(1, 256), r3=(1, 256),
+                 p2=(2, 128), s31=(2, 256), s32=(2, 256), cat3=(2, 512), r2=(2, 512), p3=(3, 256), s41=(3, 512),
+                 s42=(3, 512), cat4=(3, 1024), r1=(3, 512), p4=(4, 512), s51=(4, 512))
+    F32 = dict(f0=(0, 128), f1=(1, 256), f2=(2, 512), f3=(3, 512), f4=(4, 512), lg0=(0, 1), out=(0, 1))
+    ZEROED = ("x",)  # allocated zeroed: the first layer's slabs are only partly written
 
     def __init__(self, model):
         self.m = model
         self.dev = model.device
-        self.convs = {}
-        self.bias8 = None
-        for name, cin, cout in LAYERS:
-            w, b = model.params[name]
-            if name == "conv1_1":
-                cin = 16  # 6 slabs of 16 (8 live): 96 channels, whole 32-channel granules for the patch kernel
-            if name == "conv1_5":
-                # the cout-1 head over 6 x 128 channels as three 256-channel MFMA-head chunks [l m | h m | h h],
-                # the smallest first, each adding the previous chunk's logits (vm_conv3x3_head_acc_nhwc)
-                wf = split6_filter(w, cin, 1)
-                self.head = [ops.PackedConv(wf[:, :, 256 * k:256 * (k + 1)].contiguous(), b if k == 0 else None,
-                                            "bf16", self.dev) for k in range(3)]
-                self.convs[name] = self.head[0]
-                continue
-            pc = ops.PackedConv(split6_filter(w, cin, cout), b, "bf16", self.dev)
-            self.convs[name] = pc
+        self.convs, self.head, self.up = {}, None, {}
+        for name, cin, cout in self.LAYERS:
+            self.convs[name] = self.pack(name, cin, cout, *model.params[name])
         self._b, self._key = None, None
+        self.logits = None
 
     def weights_flat(self):
         out = []
-        for pc in [self.convs[k] for k in sorted(self.convs) if k != "conv1_5"] + self.head:
+        for pc in ([self.convs[k] for k in sorted(self.convs) if k != "conv1_5"] + self.head +
+                   [self.up[k] for k in sorted(self.up)]):
             out.append(pc.packed)
-            if pc.bias is not None:
-                out.append(pc.bias)
+            out += [t for t in (pc.bias, pc.scale, pc.shift) if t is not None]
         return out
 
-    def _buffers(self, n, h, w):
-        if self._key == (n, h, w):
-            return self._b
-        from .unet import _levels
+    def plan(self, n, h, w):
+        """The buffer set of an [n,h,w] batch, {name: (shape, dtype, zeroed)}: a pure function of the shape and the
+        class's constants (``_buffers`` allocates it)."""
         L = _levels(h, w)
-        dev = self.dev
-        S = lambda lv, c: torch.empty((n, L[lv][0], L[lv][1], 6 * c), dtype=torch.bfloat16, device=dev)  # noqa
-        F = lambda lv, c: torch.empty((n, L[lv][0], L[lv][1], c), dtype=torch.float32, device=dev)  # noqa
-        b = {"x": torch.zeros((n, L[0][0], L[0][1], 6 * 16), dtype=torch.bfloat16, device=dev), "s11": S(0, 64), "cat1": S(0, 128), "r4": S(0, 128),
-             "p1": S(1, 64), "s21": S(1, 128), "cat2": S(1, 256), "r3": S(1, 256),
-             "p2": S(2, 128), "s31": S(2, 256), "s32": S(2, 256), "cat3": S(2, 512), "r2": S(2, 512),
-             "p3": S(3, 256), "s41": S(3, 512), "s42": S(3, 512), "cat4": S(3, 1024), "r1": S(3, 512),
-             "p4": S(4, 512), "s51": S(4, 512),
-             "f0": F(0, 128), "f1": F(1, 256), "f2": F(2, 512), "f3": F(3, 512), "f4": F(4, 512),
-             "rr0": F(0, 128), "rr1": F(1, 256), "rr2": F(2, 512), "rr3": F(3, 512),
-             "lg0": F(0, 1), "lg1": F(0, 1), "lg2": F(0, 1), "zero": torch.zeros((n, L[0][0], L[0][1], 1), device=dev),
-             "out": F(0, 1)}
-        self._b, self._key = b, (n, h, w)
-        return b
+        rows = [(k, lv, self.SLABS * c, self.DTYPE) for k, (lv, c) in dict(self.SPLIT, x=(0, self.x_width())).items()]
+        rows += [(k, lv, c, torch.float32) for k, (lv, c) in self.F32.items()]
+        return {k: ((n,) + L[lv] + (c,), dt, k in self.ZEROED) for k, lv, c, dt in rows}
+
+    def _buffers(self, n, h, w):
+        if self._key != (n, h, w):
+            self._b = {k: (torch.zeros if zeroed else torch.empty)(shape, dtype=dt, device=self.dev)
+                       for k, (shape, dt, zeroed) in self.plan(n, h, w).items()}
+            self._key = (n, h, w)
+        return self._b
+
+    def whole(self, buf):
+        """The split-layout view of all channels of a SLABS*S-wide split buffer."""
+        return buf[..., :buf.shape[-1] // self.SLABS]
+
+    @staticmethod
+    def seg(buf, off, c):
+        """The split-layout view of channels [off, off + c) of a SLABS*S-wide split buffer: a [n,h,w,c] view starting
+        at channel off whose rows are SLABS*S wide (the writers put the slabs at p*S + off)."""
+        return buf[..., off:off + c]
+
+    def f32(self, name):
+        """Conv ``name``'s f32 scratch: its cout channels of its level's buffer."""
+        return self._b["f%d" % LEVEL[name]][..., :COUT[name]]
+
+    def level(self, src, name, r, up, y):
+        """conv ``name`` (relu) over the buffer ``src`` -> f32 -> resize -> split into ``r`` -> conv ``up`` (no bias, no
+        relu) into the view y, the next concat's up range (unet.py:191-200)."""
+        b = self._b
+        f = self.conv(b[src], name, self.f32(name))
+        self.resize_split(f, self.whole(b[r]), LEVEL[up])
+        self.conv_split(b[r], up, self.f32(up), y, None, "none")
 
     def forward(self, x, out=None):
         """x: [N,H,W,C] f32 frames (C = 7 video / 6 image) -> alpha [N,H,W,1] f32 (``out`` if given)."""
-        from .unet import _levels
-        n, h, w, c = x.shape
+        n, h, w, _ = x.shape
         b = self._buffers(n, h, w)
-        L = _levels(h, w)
-        C = self.convs
-        split6(x, b["x"][..., :8])  # 6 slabs of 16 channels, 8 written (the rest stay zero)
+        self.first(x, b["x"][..., :8])  # channels 0..7 of each slab (the frame's 7 or 6 and zeros); the rest stay zero
 
-        def conv(src, name, dst_f32, act="relu"):
-            return ops.conv3x3(src, C[name], act, out=dst_f32, affine=False, splitk=True)
+        def step(src, name, dst, pool=None):
+            """conv (relu) -> split into all of ``dst``, or with a pool (-> its split into ``pool``) into the skip
+            range of the concat ``dst``"""
+            y = self.whole(b[dst]) if pool is None else self.seg(b[dst], COUT[name], COUT[name])
+            self.conv_split(b[src], name, self.f32(name), y, pool and self.whole(b[pool]), "relu")
 
-        def resize_split(f_src, lv, rr_f32, r_split):
-            ops.resize_bilinear(f_src, L[lv], out=rr_f32)
-            split6(rr_f32, r_split)
+        def level(src, name, r, up, cat):
+            self.level(src, name, r, up, self.seg(b[cat], 0, COUT[up]))
 
-        f0, f1, f2, f3, f4 = b["f0"], b["f1"], b["f2"], b["f3"], b["f4"]
         # encoder (unet.py:170-189)
-        split6(conv(b["x"], "conv1_1", f0[..., :64]), whole(b["s11"]))
-        split6(conv(b["s11"], "conv1_2", f0[..., :64]), seg(b["cat1"], 64, 64), pool=whole(b["p1"]))
-        split6(conv(b["p1"], "conv2_1", f1[..., :128]), whole(b["s21"]))
-        split6(conv(b["s21"], "conv2_2", f1[..., :128]), seg(b["cat2"], 128, 128), pool=whole(b["p2"]))
-        split6(conv(b["p2"], "conv3_1", f2[..., :256]), whole(b["s31"]))
-        split6(conv(b["s31"], "conv3_2", f2[..., :256]), whole(b["s32"]))
-        split6(conv(b["s32"], "conv3_3", f2[..., :256]), seg(b["cat3"], 256, 256), pool=whole(b["p3"]))
-        split6(conv(b["p3"], "conv4_1", f3), whole(b["s41"]))
-        split6(conv(b["s41"], "conv4_2", f3), whole(b["s42"]))
-        split6(conv(b["s42"], "conv4_3", f3), seg(b["cat4"], 512, 512), pool=whole(b["p4"]))
-        split6(conv(b["p4"], "conv5_1", f4), whole(b["s51"]))
-        y52 = conv(b["s51"], "conv5_2", f4)
+        step("x", "conv1_1", "s11")
+        step("s11", "conv1_2", "cat1", "p1")
+        step("p1", "conv2_1", "s21")
+        step("s21", "conv2_2", "cat2", "p2")
+        step("p2", "conv3_1", "s31")
+        step("s31", "conv3_2", "s32")
+        step("s32", "conv3_3", "cat3", "p3")
+        step("p3", "conv4_1", "s41")
+        step("s41", "conv4_2", "s42")
+        step("s42", "conv4_3", "cat4", "p4")
+        step("p4", "conv5_1", "s51")
         # decoder: resize (f32) -> split -> conv (no bias, no relu) into the concat's up range (unet.py:191-200)
-        resize_split(y52, 3, b["rr3"], whole(b["r1"]))
-        split6(conv(b["r1"], "upconv_1", f3, act="none"), seg(b["cat4"], 0, 512))
-        y44 = conv(b["cat4"], "conv4_4", f3)
-        resize_split(y44, 2, b["rr2"], whole(b["r2"]))
-        split6(conv(b["r2"], "upconv_2", f2[..., :256], act="none"), seg(b["cat3"], 0, 256))
-        y34 = conv(b["cat3"], "conv3_4", f2[..., :256])
-        resize_split(y34, 1, b["rr1"], whole(b["r3"]))
-        split6(conv(b["r3"], "upconv_3", f1[..., :128], act="none"), seg(b["cat2"], 0, 128))
-        y23 = conv(b["cat2"], "conv2_3", f1[..., :128])
-        resize_split(y23, 0, b["rr0"], whole(b["r4"]))
-        split6(conv(b["r4"], "upconv_4", f0[..., :64], act="none"), seg(b["cat1"], 0, 64))
-        # conv1_5 + sigmoid (unet.py:203-205): three 256-channel chunks of the split cat1, logits accumulated,
-        # the sigmoid from the last
+        level("s51", "conv5_2", "r1", "upconv_1", "cat4")
+        level("cat4", "conv4_4", "r2", "upconv_2", "cat3")
+        level("cat3", "conv3_4", "r3", "upconv_3", "cat2")
+        level("cat2", "conv2_3", "r4", "upconv_4", "cat1")
+        # conv1_5 + sigmoid (unet.py:203-205)
         alpha = b["out"] if out is None else out
-        lg = [b["lg0"], b["lg1"], b["lg2"]]
-        for k in range(3):
-            xv, yv = ops.nhwc(b["cat1"][..., 256 * k:256 * (k + 1)]), ops.nhwc(lg[k])
-            pc = self.head[k]
-            ops.check(ops.lib().vm_conv3x3_head_acc_nhwc(
-                ops.ctypes.byref(xv), ops._ptr(pc.packed), 256, ops._ptr(pc.bias),
-                ops._ptr(lg[k - 1] if k else b["zero"]), ops.ctypes.byref(yv),
-                ops._ptr(alpha if k == 2 else None), ops.stream_handle()), "conv3x3_head_acc")
-        self.logits = lg[2]
+        self.logits = self.run_head(alpha)
         return alpha
+
+
+class Split6Forward(SplitForward):
+    """The split-bf16 x6 forward of a UNet (unet.UNetVideo / UNetImage) with its parameters."""
+
+    SLABS, DTYPE, LAYERS = 6, torch.bfloat16, LAYERS
+    # + the resize targets per level, the head's chunk logits and the zero logits its first chunk adds
+    F32 = dict(SplitForward.F32, rr0=(0, 128), rr1=(1, 256), rr2=(2, 512), rr3=(3, 512), lg1=(0, 1), lg2=(0, 1),
+               zero=(0, 1))
+    ZEROED = ("x", "zero")
+
+    def x_width(self):
+        return 16
+
+    def pack(self, name, cin, cout, w, b):
+        if name == "conv1_5":
+            # the cout-1 head over 6 x 128 channels as three 256-channel MFMA-head chunks [l m | h m | h h],
+            # the smallest first, each adding the previous chunk's logits (vm_conv3x3_head_acc_nhwc)
+            wf = split6_filter(w, cin, 1)
+            self.head = [ops.PackedConv(wf[:, :, 256 * k:256 * (k + 1)].contiguous(), b if k == 0 else None,
+                                        "bf16", self.dev) for k in range(3)]
+            return self.head[0]
+        return ops.PackedConv(split6_filter(w, cin, cout), b, "bf16", self.dev)
+
+    def first(self, x, y):
+        split6(x, y)
+
+    def conv(self, src, name, dst_f32, act="relu"):
+        return ops.conv3x3(src, self.convs[name], act, out=dst_f32, affine=False, splitk=True)
+
+    def conv_split(self, src, name, dst_f32, y, pool, act):
+        split6(self.conv(src, name, dst_f32, act), y, pool)
+
+    def resize_split(self, f_src, r_split, lv):
+        rr = self._b["rr%d" % lv]
+        ops.resize_bilinear(f_src, rr.shape[1:3], out=rr)
+        split6(rr, r_split)
+
+    def run_head(self, alpha):
+        """Three 256-channel chunks of the split cat1, logits accumulated, the sigmoid from the last."""
+        b = self._b
+        lg = [b["zero"], b["lg0"], b["lg1"], b["lg2"]]
+        for k, pc in enumerate(self.head):
+            xv, yv = ops.nhwc(b["cat1"][..., 256 * k:256 * (k + 1)]), ops.nhwc(lg[k + 1])
+            ops.check(ops.lib().vm_conv3x3_head_acc_nhwc(
+                ops.ctypes.byref(xv), ops._ptr(pc.packed), 256, ops._ptr(pc.bias), ops._ptr(lg[k]),
+                ops.ctypes.byref(yv), ops._ptr(alpha if k == 2 else None), ops.stream_handle()), "conv3x3_head_acc")
+        return lg[3]
 
 
 def rerun_x6(owner, frames, out):

@@ -25,14 +25,31 @@ from . import ops
 from .graphs import capture_passes, chained
 from .weights import init_conv, load_vgg16
 
-# fresh convs in graph-build order (unet.py:191-203): scope, cin, cout, keeps bias
-NEW_CONVS = (("upconv_1", 512, 512, False), ("conv4_4", 1024, 512, True),
-             ("upconv_2", 512, 256, False), ("conv3_4", 512, 256, True),
-             ("upconv_3", 256, 128, False), ("conv2_3", 256, 128, True),
-             ("upconv_4", 128, 64, False), ("conv1_5", 128, 1, True))
+# the 20 convs in TF build order (unet.py:96-143): scope, pyramid level, cin, cout, from VGG, keeps its bias
+# (conv1_1's cin is the model's IN_CH)
+CONVS = (("conv1_1", 0, None, 64, True, True), ("conv1_2", 0, 64, 64, True, True),
+         ("conv2_1", 1, 64, 128, True, True), ("conv2_2", 1, 128, 128, True, True),
+         ("conv3_1", 2, 128, 256, True, True), ("conv3_2", 2, 256, 256, True, True),
+         ("conv3_3", 2, 256, 256, True, True), ("conv4_1", 3, 256, 512, True, True),
+         ("conv4_2", 3, 512, 512, True, True), ("conv4_3", 3, 512, 512, True, True),
+         ("conv5_1", 4, 512, 512, True, True), ("conv5_2", 4, 512, 512, True, True),
+         ("upconv_1", 3, 512, 512, False, False), ("conv4_4", 3, 1024, 512, False, True),
+         ("upconv_2", 2, 512, 256, False, False), ("conv3_4", 2, 512, 256, False, True),
+         ("upconv_3", 1, 256, 128, False, False), ("conv2_3", 1, 256, 128, False, True),
+         ("upconv_4", 0, 128, 64, False, False), ("conv1_5", 0, 128, 1, False, True))
 
-VGG_USED = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3",
-            "conv4_1", "conv4_2", "conv4_3", "conv5_1", "conv5_2")
+# fresh convs in graph-build order (unet.py:191-203): scope, cin, cout, keeps bias
+NEW_CONVS = tuple((s, ci, co, kb) for s, _, ci, co, vgg, kb in CONVS if not vgg)
+VGG_USED = tuple(s for s, _, _, _, vgg, _ in CONVS if vgg)
+LEVEL = {s: lv for s, lv, _, _, _, _ in CONVS}
+COUT = {s: co for s, _, _, co, _, _ in CONVS}
+
+
+def split_layers(first_width, head_cout):
+    """The table as a split forward packs it: (scope, channels of its split input = the concat width, cout), with
+    conv1_1's slab width and conv1_5's padded cout as given."""
+    return tuple((s, first_width if s == "conv1_1" else ci, head_cout if s == "conv1_5" else co)
+                 for s, _, ci, co, _, _ in CONVS)
 
 
 def _levels(h, w):
@@ -392,12 +409,9 @@ class UNet:
     # FLOPs of the 20 convs for an [n,h,w] batch (2 * sum H*W*9*Cin*Cout) — the roofline numerator
     def conv_flops(self, n, h, w):
         L = _levels(h, w)
-        lv = {"conv1_1": 0, "conv1_2": 0, "conv2_1": 1, "conv2_2": 1, "conv3_1": 2, "conv3_2": 2, "conv3_3": 2,
-              "conv4_1": 3, "conv4_2": 3, "conv4_3": 3, "conv5_1": 4, "conv5_2": 4, "upconv_1": 3, "conv4_4": 3,
-              "upconv_2": 2, "conv3_4": 2, "upconv_3": 1, "conv2_3": 1, "upconv_4": 0, "conv1_5": 0}
         tot = 0
         for k, (wt, _) in self.params.items():
-            hh, ww = L[lv[k]]
+            hh, ww = L[LEVEL[k]]
             cin = self.IN_CH if k == "conv1_1" else wt.shape[2]
             tot += 2 * n * hh * ww * 9 * cin * wt.shape[3]
         return tot

@@ -16,6 +16,7 @@ import torch
 from . import ops
 from .graphs import capture_passes, chained
 from .layers import BatchNorm, conv_bn
+from .unet import _levels  # (the same 5-level pyramid; train.py and the bench import it from here)
 from .weights import init_conv, load_vgg16
 
 TOWER = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3",
@@ -35,13 +36,6 @@ BN_SCOPES = {"upconv4": 96, "upconv3": 48, "upconv2": 32, "upconv1": 30}
 # bf16: convs whose input width is not a multiple of 32 read a zero-padded buffer through a channel-padded pack,
 # so they run on the patch-reuse MFMA kernel (cin % 32 == 0) instead of the generic one
 CIN_PAD = {"select1_1": 32, "upconv2": 32, "upconv3": 64, "conv3": 64}
-
-
-def _levels(h, w):
-    lv = [(h, w)]
-    for _ in range(4):
-        lv.append(((lv[-1][0] + 1) // 2, (lv[-1][1] + 1) // 2))
-    return lv
 
 
 class Vgg16:
