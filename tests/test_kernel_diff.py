@@ -72,3 +72,10 @@ def test_shipped_library_equals_itself():
         assert any(name in n for n in k), name
     # ... and no kernel defined in two units (a second copy is keyed "name#2"): the one every unit reaches
     assert sum("splitk_reduce_kernel" in n for n in k) == 1
+    # one kernel of each weight-gradient unit (wgrad, wgrad_mfma, wgrad_taps, wgrad_wide); the reduction every unit
+    # launches exists once, and no weight-gradient kernel has a second copy
+    for name in ("wgrad_kernel", "wgrad_mfma_kernel", "wgrad_taps_kernel", "wgrad_taps_dma_kernel", "wgrad_wide_kernel",
+                 "wgrad_wide_f32_kernel"):
+        assert any(name in n for n in k), name
+    assert sum("wgrad_reduce4_kernel" in n for n in k) == 1
+    assert not [n for n in k if "wgrad" in n and "#" in n]

@@ -1,5 +1,5 @@
 // Conv argument block and device helpers shared by the 3x3 conv kernels (conv3x3.hip and every conv_*.hip) and
-// wgrad.hip's MFMA kernels.  Device code only: the host side (options, launchers) is conv_dispatch.h.
+// the wgrad*.hip MFMA kernels.  Device code only: the host side (options, launchers) is conv_dispatch.h.
 #pragma once
 
 #include <type_traits>

@@ -1,4 +1,4 @@
-// What the two training units share (train.hip: element-wise backward + optimizer; wgrad.hip: conv weight gradients):
+// What the training units share (train.hip: element-wise backward + optimizer; wgrad*.hip: conv weight gradients):
 // the strided NHWC view their kernels take by value, its element accessors and the entry points' argument checks.
 #pragma once
 

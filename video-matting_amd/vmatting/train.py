@@ -11,7 +11,7 @@ warped previous alpha, train.py:245):
             (train.py:294-298; the summary scalars [loss, alpha_loss, cmp_loss] are returned)
   backward  through the trainable 'model/simple_unet' variables only (train.py:289: TRAINABLE_VARIABLES of that
             scope — conv weights and biases, BN gamma/beta); hand-written kernels (csrc/train.hip): BN backward
-            with the relu mask, conv weight gradient (csrc/wgrad.hip), conv data gradient (forward kernels on flipped weights),
+            with the relu mask, conv weight gradient (csrc/wgrad*.hip), conv data gradient (forward kernels on flipped weights),
             TF-1 resize adjoint.  The upconv biases (unet_simple.py:34, drawn but unused) get no gradient, so
             TF's apply_gradients skips them; here they are simply not parameters
   exchange  DDP: one RCCL all-reduce of the flat gradient buffer (parallel.allreduce_grads); BN statistics stay
