@@ -704,6 +704,31 @@ int vm_flow_pyramid(const uint8_t* frame, int h, int w, int levels, float* pyr, 
 int vm_flow_from_pyramids(const float* cur, const float* prev, int h, int w, int levels, int warps, int iters,
                           float alpha, float* flow, void* work, void* stream);
 
+/* ---------------------------------------------------------------- trimap propagation by optical flow
+ * One key-frame trimap carried along a clip by the flows vm_clip_feed consumes (the reference takes a trimap per frame
+ * and propagates none: no counterpart there).  propagate(prev, flow, grow) = out:
+ *   prev  uint8 [h,w]: 255 is foreground, 0 background, every other value unknown
+ *   flow  f32 [h,w,2], reader.read_flow layout, 8-byte aligned: the backward flow of the new frame
+ *   out   uint8 [h,w], only the values 0, 128, 255; it must not be prev
+ * For output pixel (x, y): xs = f32(x) + flow[y,x,0], ys = f32(y) + flow[y,x,1] (one f32 add each).  Unless
+ * 0 <= xs <= w - 1 and 0 <= ys <= h - 1 (so also for NaN and infinities) out = 128.  Else x0 = floor(xs),
+ * x1 = x0 + (xs > x0), y0 and y1 likewise: the pixels the bilinear warp touches (one for an integer target, so a zero
+ * flow is the identity).  Over the window of rows y0 - grow .. y1 + grow and columns x0 - grow .. x1 + grow, clipped to
+ * the image: out = 255 if every pixel of prev in it is foreground, 0 if every one is background, 128 otherwise.  A label
+ * survives only where the warp is unambiguous, and grow (0..8) widens the unknown band by that many pixels per step to
+ * absorb flow error.  tests/trimap_prop_ref.py restates this in numpy; the kernels match it byte for byte.
+ * Two launches (csrc/trimap_prop.hip): a class map of prev into `work` (per pixel whether its (2 grow + 1)^2 window is
+ * all foreground / all background, as bit rows: 0.25 B per pixel; skipped for grow == 0), then a gather that reads 8 B
+ * of flow and writes 1 B per pixel.
+ *   work  vm_trimap_propagate_workspace_bytes(h, w, grow) bytes, 16-byte aligned; 0 bytes for grow == 0, and then
+ *         work may be NULL
+ * No allocation and no synchronisation inside: the call can be captured in a graph.  VM_EINVAL for h or w < 1 (or
+ * h * w beyond 2^31 - 4097), grow outside 0..8, a NULL pointer, out == prev or a misaligned flow / work (checked before
+ * any HIP call); the size query returns 0 for such arguments. */
+size_t vm_trimap_propagate_workspace_bytes(int h, int w, int grow);
+int vm_trimap_propagate(const uint8_t* prev, const float* flow, int h, int w, int grow, uint8_t* out, void* work,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

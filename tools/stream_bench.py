@@ -3,10 +3,14 @@ streamed pipeline beside the resident-frames VideoMatter.  Prints one JSON line 
 profiles/ingest_stream.json.  The compose section (``--sections compose``) measures vm_matte_compose the same way: the
 three modes with per-frame and static plates, the torch route to the same bytes (float64 elementwise ops, bit-equal
 output asserted), and FrameStream with out="u8" / "over" / "bgra" interleaved in one process; it prints a second JSON
-line and writes it under "stream_bench" in profiles/compose_stream.json.
+line and writes it under "stream_bench" in profiles/compose_stream.json.  The propagate section (``--sections
+propagate``, at every size of ``--propagate-sizes``) measures vm_trimap_propagate alone for grow 0, 1 and 4 against its
+bytes-per-pixel model, the flow estimator's calls per frame, and FrameStream with per-frame trimaps, with
+trimap="propagate" on given flows and on estimated ones, interleaved in one process; it prints a third JSON line and
+writes profiles/trimap_propagate.json.
 
     python tools/stream_bench.py [--frames 64] [--chunk 8] [--height 1080] [--width 1920] [--reps 9]
-                                 [--sections ingest,compose]
+                                 [--sections ingest,compose,propagate] [--propagate-sizes 500x1200,1080x1920]
 
 Kernel times are hipEvent medians over ``--reps`` runs after a warm-up; every run of a kernel works on another of
 several buffer sets, so the 83 MB alpha of the quantise kernel does not sit in the 256 MB memory-side cache between
@@ -70,6 +74,26 @@ def event_ms(fns, reps, warmup=3):
         e1.synchronize()
         times.append(e0.elapsed_time(e1) / len(fns))
     return statistics.median(times)
+
+
+def graph_ms(fns, reps, calls=1000):
+    """Median hipEvent time of one call inside a HIP graph, for calls so short that the host could not launch them
+    back to back: ``fns`` in turn, about ``calls`` calls in all, are captured once and every timed window is one
+    replay."""
+    inner = max(1, calls // len(fns))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for fn in fns:
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(inner):
+            for fn in fns:
+                fn()
+    return event_ms([g.replay], reps) / (inner * len(fns))
 
 
 def rate(nbytes, ms):
@@ -210,6 +234,145 @@ def compose_section(a):
     print(json.dumps(res))
 
 
+def propagate_bytes_per_pixel(grow):
+    """The bytes model of one vm_trimap_propagate call, per pixel: 8 B of flow read and 1 B written by the gather;
+    1 B of prev read (by the gather itself for grow 0, else by the class-map pass); and for grow > 0 the class map,
+    two bits per pixel, written once (0.25 B) and gathered (0.25 B counted once: neighbouring pixels share words)."""
+    return 8 + 1 + 1 + (0.5 if grow else 0.0)
+
+
+def propagate_size(a, h, w):
+    from vmatting import FrameStream, ops, unet
+    from vmatting.weights import synthetic_vgg16
+    n, F, hw = a.chunk, a.frames, h * w
+    res = {}
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0)
+
+    def kernels():
+        # enough buffer sets that one round of calls streams more than the 256 MB memory-side cache
+        nsets = max(a.sets, int(300e6 / (10 * hw)) + 1)
+        coarse = torch.randint(0, 3, (nsets, (h + 7) // 8, (w + 7) // 8), generator=g, device="cuda")
+        tri = (coarse * 128).clamp(max=255).to(torch.uint8).repeat_interleave(8, 1).repeat_interleave(8, 2)
+        tri = tri[:, :h, :w].contiguous()  # blocks of 0 / 128 / 255, 8 pixels wide
+        flow = (torch.rand((nsets, h, w, 2), generator=g, device="cuda") - 0.5) * 6.0  # +-3 px
+        outs = torch.empty((nsets, h, w), dtype=torch.uint8, device="cuda")
+        out = {"buffer_sets": nsets}
+        for grow in (0, 1, 4):
+            work = torch.empty(max(ops.trimap_propagate_workspace_bytes(h, w, grow), 1), dtype=torch.uint8, device="cuda")
+            ms = graph_ms([lambda i=i: ops.trimap_propagate(tri[i], flow[i], grow, out=outs[i], work=work)
+                           for i in range(nsets)], a.reps)
+            bpp = propagate_bytes_per_pixel(grow)
+            out["trimap_propagate_grow%d" % grow] = dict(rate(hw * bpp, ms), us=round(ms * 1e3, 2), bytes_per_pixel=bpp)
+        # the HBM yardstick on this box: a torch copy of 265 MB (tools/membw.py's "copy")
+        m = 1080 * 1920 * 64
+        x, y = torch.empty(m, dtype=torch.bfloat16, device="cuda"), torch.empty(m, dtype=torch.bfloat16, device="cuda")
+        ms = event_ms([lambda: y.copy_(x)], a.reps)
+        out["torch_copy_265MB"] = rate(4 * m, ms)
+        return out
+    res["kernels"] = step("propagate kernels %dx%d" % (h, w), a.step_limit, kernels)
+    torch.cuda.empty_cache()
+
+    def estimator():
+        # what flow="estimate" adds per frame: one pyramid and one flow between two pyramids
+        o = ops.FLOW_DEFAULTS
+        frames = torch.randint(0, 256, (2, h, w, 3), generator=g, device="cuda", dtype=torch.uint8)
+        floats = ops.flow_pyramid_floats(h, w, o["levels"])
+        pyr = torch.zeros((2, (floats + 3) // 4 * 4), dtype=torch.float32, device="cuda")
+        work = torch.zeros(ops.flow_workspace_bytes(h, w, o["levels"]), dtype=torch.uint8, device="cuda")
+        bw = torch.zeros((h, w, 2), dtype=torch.float32, device="cuda")
+        ops.flow_pyramid(frames[0], o["levels"], out=pyr[0], work=work)
+
+        def call():
+            ops.flow_pyramid(frames[1], o["levels"], out=pyr[1], work=work)
+            ops.flow_from_pyramids(pyr[1], pyr[0], h, w, o["levels"], o["warps"], o["iters"], o["alpha"], out=bw,
+                                   work=work)
+        return {"estimator_cost_ms_per_frame": round(graph_ms([call], a.reps, calls=20), 3)}
+    res.update(step("propagate estimator %dx%d" % (h, w), a.step_limit, estimator))
+
+    np.random.seed(0)
+    model = unet.UNetVideo(synthetic_vgg16(0), dtype="bf16", device="cuda").prepare()
+
+    def streamed():
+        rs = np.random.RandomState(1)
+        k = min(F, 2 * n)  # two distinct chunks of host frames, cycled (the source hands out views of them)
+        cmp, bg = (rs.randint(0, 256, (k, h, w, 3), dtype=np.uint8) for _ in range(2))
+        tri = rs.choice(np.array([0, 128, 255], np.uint8), (k, h, w))
+        bw = rs.uniform(-3, 3, (k, h, w, 2)).astype(np.float32)
+
+        def source(mode):
+            for i in range(0, F, n):
+                m = min(n, F - i)
+                o = i % k
+                if mode == "per_frame":
+                    yield cmp[o:o + m], bg[o:o + m], tri[o:o + m]
+                else:
+                    yield cmp[o:o + m], bg[o:o + m], (tri[0] if i == 0 else None), (bw[o:o + m] if mode == "given" else None)
+        kw = dict(chunk=n, depth=2, out="u8")
+        streams = {"per_frame": FrameStream(model, h, w, **kw),
+                   "given": FrameStream(model, h, w, trimap="propagate", flow="given", **kw),
+                   "estimate": FrameStream(model, h, w, trimap="propagate", flow="estimate", **kw)}
+
+        def run(mode):
+            t0 = time.perf_counter()
+            tot = sum(m.shape[0] for m in streams[mode].run(source(mode)))
+            torch.cuda.synchronize()
+            assert tot == F
+            return (time.perf_counter() - t0) * 1e3
+        times = {mode: [] for mode in streams}
+        for i in range(1 + max(3, a.reps // 2)):  # interleaved; round 0 warms up (and captures the graphs)
+            for mode in streams:
+                ms = run(mode)
+                if i:
+                    times[mode].append(ms)
+        out = {}
+        for mode, t in times.items():
+            ms = statistics.median(t)
+            name = "frame_stream_bf16_" + ("trimap_per_frame" if mode == "per_frame" else "propagate_" + mode)
+            out[name] = {"ms_per_frame": round(ms / F, 3), "frames_per_s": round(F / ms * 1e3, 1),
+                         "min_ms_per_frame": round(min(t) / F, 3), "max_ms_per_frame": round(max(t) / F, 3)}
+        base = out["frame_stream_bf16_trimap_per_frame"]["ms_per_frame"]
+        for mode in ("given", "estimate"):
+            out["propagate_%s_adds_ms_per_frame" % mode] = round(
+                out["frame_stream_bf16_propagate_" + mode]["ms_per_frame"] - base, 3)
+        return out
+    res.update(step("propagate streams %dx%d" % (h, w), a.step_limit, streamed))
+
+    def link():
+        """What each mode stages and uploads per frame (7 B per pixel with per-frame trimaps, 14 B with given flows, 6 B
+        with estimated ones): the host's copy into pinned memory, which is serial host work, and the upload."""
+        out = {}
+        for name, nbytes in (("per_frame_7B", 7), ("given_14B", 14), ("estimate_6B", 6)):
+            hb = torch.empty(n * hw * nbytes, dtype=torch.uint8).pin_memory()
+            db = torch.empty(n * hw * nbytes, dtype=torch.uint8, device="cuda")
+            ms = event_ms([lambda: db.copy_(hb, non_blocking=True)], a.reps)
+            out["h2d_pinned_" + name] = {"ms_per_frame": round(ms / n, 3), "GBps": round(n * hw * nbytes / ms / 1e6, 1)}
+            src = np.frombuffer(np.random.RandomState(2).bytes(hb.numel()), np.uint8)
+            t0 = time.perf_counter()
+            for _ in range(3):
+                hb.numpy()[...] = src
+            ms = (time.perf_counter() - t0) / 3 * 1e3
+            out["host_copy_" + name] = {"ms_per_frame": round(ms / n, 3), "GBps": round(n * hw * nbytes / ms / 1e6, 1)}
+        return out
+    res["link"] = step("propagate link %dx%d" % (h, w), a.step_limit, link)
+    del model
+    torch.cuda.empty_cache()
+    return res
+
+
+def propagate_section(a):
+    res = {"chunk": a.chunk, "frames": a.frames, "reps": a.reps, "device": torch.cuda.get_device_name(0),
+           "hbm_peak_GBps": HBM_PEAK / 1e9, "grow_of_streams": 1, "sizes": {}}
+    for size in a.propagate_sizes.split(","):
+        h, w = (int(v) for v in size.split("x"))
+        res["sizes"][size] = propagate_size(a, h, w)
+    line = json.dumps(res)
+    os.makedirs(os.path.dirname(a.propagate_out), exist_ok=True)
+    with open(a.propagate_out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
@@ -221,11 +384,13 @@ def main():
     ap.add_argument("--step-limit", type=int, default=150)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ingest_stream.json"))
     ap.add_argument("--compose-out", default=os.path.join(REPO, "profiles", "compose_stream.json"))
-    ap.add_argument("--sections", default="ingest,compose", help="comma-separated: ingest, compose")
+    ap.add_argument("--propagate-out", default=os.path.join(REPO, "profiles", "trimap_propagate.json"))
+    ap.add_argument("--propagate-sizes", default="500x1200,1080x1920", help="comma-separated HxW of the propagate section")
+    ap.add_argument("--sections", default="ingest,compose", help="comma-separated: ingest, compose, propagate")
     a = ap.parse_args()
     sections = set(a.sections.split(","))
-    if not sections or sections - {"ingest", "compose"}:
-        raise SystemExit("stream_bench: --sections takes ingest and / or compose, got %r" % a.sections)
+    if not sections or sections - {"ingest", "compose", "propagate"}:
+        raise SystemExit("stream_bench: --sections takes ingest, compose and / or propagate, got %r" % a.sections)
     if not torch.cuda.is_available():
         raise SystemExit("stream_bench needs a ROCm GPU")
     if "ingest" in sections:
@@ -233,6 +398,9 @@ def main():
         torch.cuda.empty_cache()
     if "compose" in sections:
         compose_section(a)
+        torch.cuda.empty_cache()
+    if "propagate" in sections:
+        propagate_section(a)
 
 
 def ingest_section(a):

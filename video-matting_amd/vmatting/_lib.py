@@ -201,6 +201,8 @@ SIGNATURES = [
     ("vm_flow_pyramid", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("vm_flow_from_pyramids", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                       c_void_p, c_void_p]),
+    ("vm_trimap_propagate_workspace_bytes", c_size_t, [c_int, c_int, c_int]),
+    ("vm_trimap_propagate", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 ]
 
 _lib = None

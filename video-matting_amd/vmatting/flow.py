@@ -60,6 +60,26 @@ def estimate_flow(cur, prev, levels=6, warps=3, iters=20, alpha=15.0):
     return out.cpu().numpy()
 
 
+def propagate_trimap(trimap, backward, grow=1):
+    """The trimap of the next frame from the previous frame's uint8 [H,W] ``trimap`` (255 foreground, 0 background,
+    anything else unknown) and the next frame's ``backward`` flow, f32 [H,W,2] as estimate_flow(next, previous)
+    returns it: a label survives where every pixel the bilinear warp would touch, and every pixel within ``grow``
+    (0..8) of those, carries it; the rest is 128 (ops.trimap_propagate).  The reference takes a trimap per frame and
+    propagates none.  numpy arrays return numpy, device tensors stay on the device."""
+    if isinstance(trimap, torch.Tensor) != isinstance(backward, torch.Tensor):
+        raise TypeError("propagate_trimap: trimap and backward are both numpy arrays or both torch tensors")
+    if isinstance(trimap, torch.Tensor):
+        return ops.trimap_propagate(trimap.contiguous(), backward.contiguous(), grow)
+    t, b = np.ascontiguousarray(trimap), np.ascontiguousarray(backward)
+    if t.dtype != np.uint8 or b.dtype != np.float32:
+        raise TypeError("propagate_trimap: a uint8 trimap and a float32 flow expected, got %s and %s" % (t.dtype, b.dtype))
+    if t.ndim != 2 or b.shape != t.shape + (2,):
+        raise ValueError("propagate_trimap: an [H,W] trimap and an [H,W,2] flow expected, got %s and %s" %
+                         (t.shape, b.shape))
+    ops.check_grow("propagate_trimap", grow)
+    return ops.trimap_propagate(torch.from_numpy(t).cuda(), torch.from_numpy(b).cuda(), grow).cpu().numpy()
+
+
 def correct_alpha(backward, forward, alpha, promote="numpy1", thresh=15.0):
     """flow.correct_alpha (flow.py:36-65): zero alpha where the forward/backward round trip misses by > 15 px.
 

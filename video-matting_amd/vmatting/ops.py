@@ -1130,6 +1130,57 @@ def estimate_flow(cur_u8, prev_u8, levels=6, warps=3, iters=20, alpha=15.0, out=
     return out.view(h, w, 2)
 
 
+# ---------------------------------------------------------------- trimap propagation by optical flow
+
+GROW_MAX = 8
+
+
+def check_grow(who, grow):
+    """``grow`` as vm_trimap_propagate checks it, on the host: an integer in 0..8."""
+    if isinstance(grow, bool) or not isinstance(grow, (int, np.integer)):
+        raise TypeError("%s: grow must be an integer, got %r" % (who, grow))
+    if not 0 <= grow <= GROW_MAX:
+        raise ValueError("%s: grow must be in 0..%d, got %d" % (who, GROW_MAX, grow))
+    return int(grow)
+
+
+def trimap_propagate_workspace_bytes(h, w, grow):
+    return lib().vm_trimap_propagate_workspace_bytes(h, w, grow)
+
+
+def trimap_propagate(prev, flow, grow=1, out=None, work=None):
+    """vm_trimap_propagate: the trimap of the next frame from ``prev`` (uint8 [h,w]: 255 foreground, 0 background,
+    anything else unknown) and that frame's backward flow (f32 [h,w,2], reader.read_flow layout, as estimate_flow
+    returns it) -> uint8 [h,w] of 0 / 128 / 255.  A label survives where every pixel of prev the bilinear warp would
+    touch, and every pixel within ``grow`` (0..8) of those, carries it (include/vmatting.h).  ``out``: a contiguous
+    uint8 [h,w] device tensor that is not ``prev``; ``work``: a uint8 device buffer of
+    trimap_propagate_workspace_bytes(h, w, grow); both are allocated when None."""
+    who = "trimap_propagate"
+    for name, t, dt in (("prev", prev, torch.uint8), ("flow", flow, torch.float32)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
+        if t.dtype != dt:
+            raise TypeError("%s: %s must be %s, got %s" % (who, name, dt, t.dtype))
+    if prev.dim() != 2 or prev.shape[0] < 1 or prev.shape[1] < 1:
+        raise ValueError("%s: prev must be [h,w], got %s" % (who, tuple(prev.shape)))
+    h, w = (int(v) for v in prev.shape)
+    if tuple(flow.shape) != (h, w, 2):
+        raise ValueError("%s: flow must be [h,w,2] = %s, got %s" % (who, (h, w, 2), tuple(flow.shape)))
+    for name, t in (("prev", prev), ("flow", flow)):
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (who, name))
+        _require_gpu(t)
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (h, w)):
+        raise ValueError("%s: out must be [h,w] = %s, got %s" % (who, (h, w), tuple(getattr(out, "shape", ()))))
+    out = _flow_buffer(who, "out", out, h * w, torch.uint8, prev.device)
+    if isinstance(grow, bool) or not isinstance(grow, (int, np.integer)):
+        raise TypeError("%s: grow must be an integer, got %r" % (who, grow))
+    grow = int(grow)  # (its range is the library's check: the size query gives 0 outside it)
+    work = _flow_buffer(who, "work", work, trimap_propagate_workspace_bytes(h, w, grow), torch.uint8, prev.device)
+    check(lib().vm_trimap_propagate(_ptr(prev), _ptr(flow), h, w, grow, _ptr(out), _ptr(work), stream_handle()), who)
+    return out.view(h, w)
+
+
 # ---------------------------------------------------------------- training step (train.py:288-343, config 5)
 
 def matting_loss_backward(pred, gt, raw_fg, in_bg, in_cmp, out=None):

@@ -13,6 +13,11 @@ static buffers on one stream; a short chunk runs the same calls eagerly on leadi
 is the matte of ``model.forward`` on the reference's feed of that frame (loader.py:45,75-78: the float64 mean
 subtraction rounded to f32 once), bit for bit, then quantised.
 
+``trimap="propagate"``: the user has one trimap per shot, not one per frame.  Source items then carry a key trimap
+(or None: continue) and the frames' backward flows (or None with ``flow="estimate"``: estimated from the frames), and
+the chunk's chain starts with the recurrence tri[j] = ops.trimap_propagate(tri[j-1], backward[j], grow).  It depends on
+the frames only, never on the model's output, so the forward stays chunked.
+
 This is one process's share of a clip; sharding a clip across ranks stays video.shard's job.
 """
 
@@ -24,6 +29,9 @@ from .pipeline import OUT_DTYPES  # noqa: F401  (public)
 from .pipeline import PER_FRAME, Slot, SlotPipeline, check_new_bg, check_out, check_static_bg
 from .split6 import rerun_x6
 
+PROPAGATE = "propagate"
+FLOW_MODES = ("given", "estimate")
+
 
 class _Slot(Slot):
     """One chunk in flight: pinned host inputs, their device copies, the frame buffer in the model's input format,
@@ -32,11 +40,19 @@ class _Slot(Slot):
     def __init__(self, fs):
         n, h, w = fs.chunk, fs.h, fs.w
         u8 = torch.uint8
+        given = fs.propagate and not fs.estimate
         super().__init__(fs.device, (("cmp", (n, h, w, 3), u8),
                                      ("bg", (n, h, w, 3) if fs.static_bg is None else None, u8),
-                                     ("tri", (n, h, w) if fs.trimap else None, u8),
+                                     ("tri", (n, h, w) if fs.trimap and not fs.propagate else None, u8),
+                                     ("key", (1, h, w) if fs.propagate else None, u8),
+                                     ("bw", (n, h, w, 2) if given else None, torch.float32),
                                      ("nw", (n, h, w, 3) if fs.new_bg is PER_FRAME else None, u8)),
                          n, h, w, fs.out, flag=fs.model.split_mode == "f16x3")  # f16x3: this slot's range flag
+        if fs.propagate:  # the chunk's trimaps are made on the device: no pinned twin, nothing uploaded
+            self.d_tri = torch.zeros((n, h, w), dtype=u8, device=fs.device)
+            if fs.estimate:
+                self.d_bw = torch.zeros((n, h, w, 2), dtype=torch.float32, device=fs.device)
+        self.graphs = {}  # trimap="propagate": the full-chunk graph of a keyed item (True) and of a continued one
         self.frames = ops.frame_buffer(fs.model, n, h, w)
         self.alpha = torch.empty((n, h, w, 1), dtype=torch.float32, device=fs.device)
         self.graph = None
@@ -58,18 +74,53 @@ class FrameStream(SlotPipeline):
     Results lag the source by ``depth - 1`` chunks.  On an f16x3 model a chunk whose activations leave fp16's range is
     run again on bf16x6 before it is yielded and its index is appended to ``overflowed_chunks``.
 
+    ``trimap="propagate"`` (a 7-channel model): the trimaps are propagated on the device from key trimaps by the
+    frames' backward flows.  Source items are ``(cmp, bg, key, backward)`` (and new_bg last with "per_frame").
+    ``key``: the uint8 [h,w] trimap of the item's first frame, or None to continue from the previous item's last
+    frame; the first item of a run carries one, and a later one restarts the chain there.  ``backward``: f32
+    [k,h,w,2], frame j's flow into frame j - 1 in reader.read_flow layout (entry 0 is unused when the item has a key);
+    None exactly when ``flow="estimate"`` (the default with "propagate"; ``flow="given"`` is the other mode), which
+    estimates it from consecutive frames (ops.estimate_flow's arithmetic, ``flow_options`` its levels / warps / iters /
+    alpha; h and w at least 16).  Frame j's trimap is
+    ops.trimap_propagate(trimap of frame j - 1, backward[j], grow): a label survives where the warp is unambiguous, and
+    ``grow`` (0..8) widens the unknown band by that many pixels per frame to absorb flow error.  The mattes are those
+    of ``trimap=True`` fed with these trimaps, bit for bit.  ``last_trimap()`` returns the last frame's trimap after a
+    run: inspect its drift to place the next key.
+
     If the source raises, or yields a wrong shape, dtype or k, the chunks already taken are finished and yielded, the
     streams are synchronised, and the exception then propagates; the object can run again."""
 
-    def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True, new_bg=None):
+    def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True, new_bg=None,
+                 flow=None, flow_options=None, grow=1):
         h, w, chunk, depth = int(h), int(w), int(chunk), int(depth)
         if h < 1 or w < 1 or chunk < 1 or depth < 1:
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
                              (h, w, chunk, depth))
         check_out("FrameStream", out)
+        self.propagate = isinstance(trimap, str)
+        if self.propagate and trimap != PROPAGATE:
+            raise ValueError("FrameStream: trimap must be True, False or %r, got %r" % (PROPAGATE, trimap))
         if (7 if trimap else 6) != model.IN_CH:
             raise ValueError("FrameStream: %s takes %d channels, so trimap must be %s" %
-                             (type(model).__name__, model.IN_CH, model.IN_CH == 7))
+                             (type(model).__name__, model.IN_CH,
+                              "True or %r" % PROPAGATE if model.IN_CH == 7 else False))
+        if not self.propagate and (flow is not None or flow_options is not None):
+            raise ValueError("FrameStream: flow and flow_options go with trimap=%r" % PROPAGATE)
+        self.grow = ops.check_grow("FrameStream", grow)
+        flow = "estimate" if flow is None else flow
+        if flow not in FLOW_MODES:
+            raise ValueError("FrameStream: flow must be one of %s, got %r" % (FLOW_MODES, flow))
+        self.estimate = self.propagate and flow == "estimate"
+        if flow_options is not None and not self.estimate:
+            raise ValueError("FrameStream: flow_options go with flow='estimate'")
+        if self.estimate:
+            opts = dict(ops.FLOW_DEFAULTS)
+            for k, v in dict(flow_options or {}).items():
+                if k not in opts:
+                    raise ValueError("FrameStream: flow_options takes %s, got %r" % (sorted(opts), k))
+                opts[k] = v
+            self.flow_options = dict(zip(("levels", "warps", "iters", "alpha"),
+                                         ops.check_flow_options("FrameStream", h, w, **opts)))
         static_bg = check_static_bg("FrameStream", static_bg, h, w)
         self.new_bg = check_new_bg("FrameStream", out, new_bg, h, w)
         self.model, self.h, self.w, self.chunk, self.depth = model, h, w, chunk, depth
@@ -78,20 +129,31 @@ class FrameStream(SlotPipeline):
         self.overflowed_chunks = []
         self._plate = self._new_plate = None
         self._x6 = None
+        self._keyed = False      # trimap="propagate": whether this run has had its first key
+        self._tri_last = None    # ... and the last frame's trimap, at a fixed device address
 
     # ------------------------------------------------------------------ checks (host only)
     def check_item(self, item):
-        """Validate one source item; returns (cmp, bg, trimap, k), and new_bg after them with new_bg="per_frame"."""
+        """Validate one source item; returns (cmp, bg, trimap, k), and new_bg after them with new_bg="per_frame".
+        With trimap="propagate": (cmp, bg, key, k, new_bg | None, backward)."""
+        if self.propagate:
+            return self._check_propagate_item(item)
         per_frame = self.new_bg is PER_FRAME
         if not isinstance(item, (tuple, list)) or len(item) != 3 + per_frame:
             raise ValueError("FrameStream: the source yields (cmp, bg, trimap%s)" %
                              (", new_bg) with new_bg='per_frame'" if per_frame else ") triples"))
         cmp, bg, tri = item[:3]
+        k, nw = self._check_frames(cmp, bg, tri, item[3] if per_frame else None)
+        return (cmp, bg, tri, k, nw) if per_frame else (cmp, bg, tri, k)
+
+    def _check_frames(self, cmp, bg, tri, nw):
+        """The frames of one item: cmp, bg | None, the per-frame trimaps | None, and new_bg with new_bg="per_frame"
+        -> (k, new_bg)."""
         if not isinstance(cmp, np.ndarray):
             raise TypeError("FrameStream: cmp must be a numpy array, got %s" % type(cmp).__name__)
         if (bg is None) != (self.static_bg is not None):
             raise ValueError("FrameStream: bg is None exactly when a static_bg was given")
-        if (tri is None) == self.trimap:
+        if not self.propagate and (tri is None) == self.trimap:
             raise ValueError("FrameStream: trimap is None exactly when trimap=False")
         for name, a in (("bg", bg), ("trimap", tri)):
             if a is not None and not isinstance(a, np.ndarray):
@@ -103,16 +165,37 @@ class FrameStream(SlotPipeline):
             raise ValueError("FrameStream: bg must be [k,h,w,3] like cmp, got %s" % (tuple(bg.shape),))
         if k > self.chunk:
             raise ValueError("FrameStream: an item of %d frames exceeds chunk=%d" % (k, self.chunk))
-        if per_frame:
-            nw = item[3]
+        if self.new_bg is PER_FRAME:
             if not isinstance(nw, np.ndarray):
                 raise TypeError("FrameStream: new_bg must be a numpy array, got %s" % type(nw).__name__)
             if nw.dtype != np.uint8:
                 raise TypeError("FrameStream: new_bg must be uint8, got %s" % nw.dtype)
             if nw.shape != cmp.shape:
                 raise ValueError("FrameStream: new_bg must be [k,h,w,3] like cmp, got %s" % (tuple(nw.shape),))
-            return cmp, bg, tri, k, nw
-        return cmp, bg, tri, k
+        return k, nw
+
+    def _check_propagate_item(self, item):
+        per_frame = self.new_bg is PER_FRAME
+        if not isinstance(item, (tuple, list)) or len(item) != 4 + per_frame:
+            raise ValueError("FrameStream: with trimap='propagate' the source yields (cmp, bg, key, backward%s)" %
+                             (", new_bg) with new_bg='per_frame'" if per_frame else ")"))
+        cmp, bg, key, bw = item[:4]
+        if key is None and not self._keyed:
+            raise ValueError("FrameStream: the first item of a run carries a key trimap")
+        if (bw is None) != self.estimate:
+            raise ValueError("FrameStream: backward is None exactly when flow='estimate'")
+        for name, a, dt in (("key", key, np.uint8), ("backward", bw, np.float32)):
+            if a is not None and not isinstance(a, np.ndarray):
+                raise TypeError("FrameStream: %s must be a numpy array, got %s" % (name, type(a).__name__))
+            if a is not None and a.dtype != dt:
+                raise TypeError("FrameStream: %s must be %s, got %s" % (name, np.dtype(dt).name, a.dtype))
+        if key is not None and key.shape != (self.h, self.w):
+            raise ValueError("FrameStream: key must be [h,w] = %s, got %s" % ((self.h, self.w), key.shape))
+        k, nw = self._check_frames(cmp, bg, None, item[4] if per_frame else None)
+        if bw is not None and bw.shape != (k, self.h, self.w, 2):
+            raise ValueError("FrameStream: backward must be [k,h,w,2] = %s, got %s" % ((k, self.h, self.w, 2), bw.shape))
+        self._keyed = True
+        return cmp, bg, key, k, nw, bw
 
     # ------------------------------------------------------------------ device side
     def _setup(self):
@@ -122,8 +205,60 @@ class FrameStream(SlotPipeline):
             self._plate = torch.from_numpy(self.static_bg).to(self.device)
         if isinstance(self.new_bg, np.ndarray):
             self._new_plate = torch.from_numpy(self.new_bg).to(self.device)
+        if self.propagate:
+            self._setup_propagate()
         self._slots = [_Slot(self) for _ in range(self.depth)]
         torch.cuda.synchronize(self.device)  # the plates and the zeroed pad channels, before another stream reads them
+        if self.propagate and self.graph:
+            # captured here, not with the first full chunk: a capture runs its chain once to warm up, and that run
+            # would move the chain's state (the last trimap, the last pyramid) one chunk ahead of the clip
+            with torch.cuda.stream(self._compute):
+                for s in self._slots:
+                    for keyed in (True, False):
+                        self._capture(s, keyed)
+            torch.cuda.synchronize(self.device)
+
+    def _setup_propagate(self):
+        """What the trimap chain keeps between chunks, once for every slot (the chains run one after another on the
+        compute stream) and at fixed addresses (every slot's graphs read and leave it there): the last frame's trimap
+        and, with flow="estimate", the pyramids of the previous chunk's last frame (row 0) and of this chunk's frames."""
+        dev, h, w = self.device, self.h, self.w
+        self._tri_last = torch.zeros((h, w), dtype=torch.uint8, device=dev)
+        self._tri_work = torch.zeros(max(ops.trimap_propagate_workspace_bytes(h, w, self.grow), 1), dtype=torch.uint8,
+                                     device=dev)
+        if self.estimate:
+            levels = self.flow_options["levels"]
+            floats = (ops.flow_pyramid_floats(h, w, levels) + 3) // 4 * 4  # every row 16-byte aligned
+            self._pyr = torch.zeros((self.chunk + 1, floats), dtype=torch.float32, device=dev)
+            self._flow_work = torch.zeros(ops.flow_workspace_bytes(h, w, levels), dtype=torch.uint8, device=dev)
+
+    def _trimaps(self, s, k, keyed):
+        """The trimaps of the slot's first k frames into s.d_tri, on the current stream: the key or the propagated last
+        trimap for frame 0, then frame by frame; with flow="estimate" each frame's pyramid and its flow against the
+        previous frame's first.  The last trimap (and pyramid) stay behind for the next chunk."""
+        if self.estimate:
+            o, pyr = self.flow_options, self._pyr
+            for j in range(k):
+                ops.flow_pyramid(s.d_cmp[j], o["levels"], out=pyr[j + 1], work=self._flow_work)
+                if j or not keyed:
+                    ops.flow_from_pyramids(pyr[j + 1], pyr[j], self.h, self.w, o["levels"], o["warps"], o["iters"],
+                                           o["alpha"], out=s.d_bw[j], work=self._flow_work)
+            pyr[0].copy_(pyr[k])
+        for j in range(k):
+            if j == 0 and keyed:
+                s.d_tri[0].copy_(s.d_key[0])
+            else:
+                ops.trimap_propagate(s.d_tri[j - 1] if j else self._tri_last, s.d_bw[j], self.grow, out=s.d_tri[j],
+                                     work=self._tri_work)
+        self._tri_last.copy_(s.d_tri[k - 1])
+
+    def last_trimap(self):
+        """trimap="propagate": the uint8 [h,w] trimap of the last frame submitted, once the run has drained."""
+        if not self.propagate:
+            raise ValueError("FrameStream: last_trimap() goes with trimap='propagate'")
+        if self._tri_last is None:
+            raise RuntimeError("FrameStream: last_trimap() before any frame was submitted")
+        return self._tri_last.cpu().numpy()
 
     def _download(self, s, k):
         """The result of the slot's first k frames from its alpha (and, composed, its uint8 inputs)."""
@@ -131,37 +266,54 @@ class FrameStream(SlotPipeline):
         nw = self._new_plate if self._new_plate is not None else None if s.d_nw is None else s.d_nw[:k]
         s.download(s.alpha[:k], s.d_cmp[:k], bg, nw)
 
-    def _chain(self, s, k):
-        """Ingest -> forward -> quantise | compose -> download of the slot's first k frames, on the current stream."""
+    def _chain(self, s, k, keyed=False):
+        """Ingest -> forward -> quantise | compose -> download of the slot's first k frames, on the current stream;
+        with trimap="propagate" the frames' trimaps first."""
         bg = self._plate if self._plate is not None else s.d_bg[:k]
+        if self.propagate:
+            self._trimaps(s, k, keyed)
         ops.frames_from_u8(s.d_cmp[:k], bg, None if s.d_tri is None else s.d_tri[:k], out=s.frames[:k])
         self.model.forward(s.frames[:k], out=s.alpha[:k], overflow=s.flag)
         self._download(s, k)
 
-    def _capture(self, s):
+    def _capture(self, s, keyed=None):
         """The full-chunk chain of one slot as one HIP graph: UNet.capture records the forward over the slot's static
-        buffers with the ingest before it and the quantisation and download after it, all on the capturing stream."""
+        buffers with the ingest before it and the quantisation and download after it, all on the capturing stream.
+        ``keyed`` (trimap="propagate"): the graph of an item with a key, or of one that continues; the trimap chain
+        heads it."""
         bg = self._plate if self._plate is not None else s.d_bg
-        s.graph = self.model.capture(
-            s.frames, static=True, out=s.alpha, overflow=s.flag,
-            pre=lambda: ops.frames_from_u8(s.d_cmp, bg, s.d_tri, out=s.frames),
-            post=lambda: self._download(s, self.chunk))
 
-    def _submit(self, s, index, cmp, bg, tri, k, nw=None):
+        def pre():
+            if keyed is not None:
+                self._trimaps(s, self.chunk, keyed)
+            ops.frames_from_u8(s.d_cmp, bg, s.d_tri, out=s.frames)
+
+        graph = self.model.capture(s.frames, static=True, out=s.alpha, overflow=s.flag, pre=pre,
+                                   post=lambda: self._download(s, self.chunk))
+        if keyed is None:
+            s.graph = graph
+        else:
+            s.graphs[keyed] = graph
+
+    def _submit(self, s, index, cmp, bg, tri, k, nw=None, bw=None):
         s.k, s.index = k, index
-        for name, a in (("cmp", cmp), ("bg", bg), ("tri", tri), ("nw", nw)):
-            s.stage(name, a, k)
+        keyed = self.propagate and tri is not None
+        for name, a in (("cmp", cmp), ("bg", bg), ("key" if self.propagate else "tri", tri), ("bw", bw), ("nw", nw)):
+            s.stage(name, a, 1 if name == "key" else k)
         with torch.cuda.stream(self._upload):
             s.upload(k)
             s.uploaded.record(self._upload)
         with torch.cuda.stream(self._compute):
             self._compute.wait_event(s.uploaded)
             if self.graph and k == self.chunk:
-                if s.graph is None:
-                    self._capture(s)
-                s.graph.replay()
+                if self.propagate:
+                    s.graphs[keyed].replay()
+                else:
+                    if s.graph is None:
+                        self._capture(s)
+                    s.graph.replay()
             else:
-                self._chain(s, k)
+                self._chain(s, k, keyed)
             s.done.record(self._compute)
 
     def _retire(self, s):
@@ -181,4 +333,5 @@ class FrameStream(SlotPipeline):
         """Generator: one [k,h,w] matte (numpy, the ``out`` dtype), or one composed [k,h,w,3 | 4] uint8 array, per source
         item, in source order."""
         self.overflowed_chunks = []
+        self._keyed = False
         yield from super().run(source)
