@@ -729,6 +729,59 @@ size_t vm_trimap_propagate_workspace_bytes(int h, int w, int grow);
 int vm_trimap_propagate(const uint8_t* prev, const float* flow, int h, int w, int grow, uint8_t* out, void* work,
                         void* stream);
 
+/* ---------------------------------------------------------------- matting metrics of a matte against ground truth
+ * The per-frame metrics of Rhemann et al. (SAD, MSE, gradient error) over the trimap's unknown region and the temporal
+ * metrics of Erofeev et al. (dtSSD, MESSDdt) as per-frame sums; the figures follow from the sums on the host (the
+ * reference scores nothing but its training loss: no counterpart there).  Connectivity error is not computed.
+ *   pred, gt    [n,h,w], each VM_F32 or VM_U8, independently
+ *   trimap      uint8 [n,h,w] or NULL
+ *   prev_pred, prev_gt  [h,w] with the dtypes of pred and gt, or both NULL: the frame before frame 0 of this call
+ *   backward    f32 [n,h,w,2] or NULL, reader.read_flow layout, 8-byte aligned: frame j's flow into frame j - 1, what
+ *               vm_clip_feed and vm_trimap_propagate consume
+ *   stats       f64 [n,8], 8-byte aligned;  grad_map f32 [n,h,w] or NULL
+ * Per pixel everything is f32, nothing contracted, IEEE division and sqrt:
+ *   unit value  U(q) = (float)q / 255.f of a uint8, U(v) = min(max(v, 0), 1) of an f32 with NaN -> 0 (vm_matte_compose's
+ *               clamp); a = U(pred), g = U(gt)
+ *   region R_j  with a trimap the pixels of frame j whose trimap byte is neither 0 nor 255 (vm_trimap_propagate's
+ *               "unknown"); without one every pixel
+ *   terms       d = a - g; sad = |d|; sse = d * d
+ *   gradient    Gaussian first-derivative filters, sigma 1.4, radius 4 (9 x 9), replicated borders.  Taps for i = -4..4:
+ *               g_i = exp(-i^2 / (2 sigma^2)), d_i = -i g_i, G = g / sqrt(sum g^2), D = d / sqrt(sum d^2), computed in
+ *               float64 and rounded to f32:
+ *                 G = 0.010715649f 0.0639064f 0.22881863f 0.4918805f 0.63481766f 0.4918805f 0.22881863f 0.0639064f
+ *                     0.010715649f
+ *                 D = 0.04329901f 0.19367121f 0.46229678f 0.49688867f +0.0f -0.49688867f -0.46229678f -0.19367121f
+ *                     -0.04329901f
+ *               a 1-D pass is acc = 0; for k = -4..4 ascending: acc = acc + tap[k] * v[clamped index + k];
+ *               gx = vertical_G(horizontal_D(x)), gy = vertical_D(horizontal_G(x)), m(x) = sqrtf(gx * gx + gy * gy);
+ *               grad = (m(a) - m(g))^2.  The filters read neighbours outside the region; only the sum is restricted.
+ *   temporal    for frame j >= 1 against frame j - 1 of the same arrays, for frame 0 against prev_* (without prev_* all
+ *               three temporal entries of frame 0 are 0); (a', g') the previous frame's unit values:
+ *               dt = ((a - a') - (g - g'))^2, summed over R_j
+ *   MESSDdt     only with backward b: xs = f32(x) + b[0], ys = f32(y) + b[1]; a pixel takes part only if 0 <= xs <= w - 1
+ *               and 0 <= ys <= h - 1 (NaN and infinities drop out).  e' = (a' - g')^2 at x0 = floor(xs),
+ *               x1 = min(x0 + 1, w - 1), y likewise; fx = xs - x0, fy = ys - y0; top = e'00 + fx * (e'01 - e'00), bot
+ *               likewise, e^ = top + fy * (bot - top) (vm_flow_estimate's bilinear); me = |sse - e^| summed over the
+ *               pixels of R_j that take part, and they are counted
+ *   sums        float64, every f32 term converted before it is added; per-block partials and a fold in a fixed order, no
+ *               atomics: the same inputs give the same bits on every run
+ * stats row j: [0] pixels in R_j, [1] sum sad, [2] sum sse, [3] sum grad, [4] sum dt, [5] sum me, [6] pixels that took
+ * part in [5], [7] 0; entries 4 - 6 are 0 where they do not apply.  grad_map receives grad of every pixel, whatever its
+ * region.  Figures: SAD = [1], MSE = [2] / [0], Grad = [3], dtSSD = sqrt([4] / [0]), MESSDdt = [5] / [6] (published
+ * tables usually quote SAD / 1000, MSE * 1000 and Grad / 1000).  tests/score_ref.py restates all of this in numpy; the
+ * kernel's counts and grad_map equal it exactly and each sum is the restatement's f32 terms added in f64.
+ * One fused launch over 64 x 16 tiles with a 4-pixel halo in LDS, then a fold (csrc/score.hip); 16-byte f32 / dword
+ * uint8 loads when the plane is so aligned and w is a multiple of 4, else element by element, the same bits.
+ *   work  vm_matte_score_workspace_bytes(n, h, w) bytes, 8-byte aligned
+ * No allocation and no synchronisation inside: the call can be captured in a graph.  VM_EINVAL for a NULL pred / gt /
+ * stats / work, n, h or w < 1 (or more than 2^23 tiles), a dtype other than VM_F32 / VM_U8, only one of prev_pred /
+ * prev_gt, a misaligned backward / stats / work or an f32 plane off 4 bytes (checked before any HIP call); the size
+ * query returns 0 for such shapes. */
+size_t vm_matte_score_workspace_bytes(int n, int h, int w);
+int vm_matte_score(const void* pred, int pred_dtype, const void* gt, int gt_dtype, const uint8_t* trimap,
+                   const void* prev_pred, const void* prev_gt, const float* backward, int n, int h, int w,
+                   double* stats, float* grad_map, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ from . import _lib, ops, weights  # noqa: F401
 from .params import VGG_MEAN  # noqa: F401
 from .stream import FrameStream  # noqa: F401
 from .clip import ClipStream  # noqa: F401
+from .score import MatteScorer  # noqa: F401
 
 __all__ = ["unet", "unet_simple", "small", "refine", "flow", "reader", "tps", "augmentation", "loader", "parallel", "ops",
-           "weights", "video", "stream", "FrameStream", "clip", "ClipStream"]
+           "weights", "video", "stream", "FrameStream", "clip", "ClipStream", "score", "MatteScorer"]

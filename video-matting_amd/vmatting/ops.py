@@ -1181,6 +1181,109 @@ def trimap_propagate(prev, flow, grow=1, out=None, work=None):
     return out.view(h, w)
 
 
+# ---------------------------------------------------------------- matting metrics against ground truth
+
+_SCORE_DT = {torch.float32: _lib.VM_F32, torch.uint8: _lib.VM_U8}
+
+
+def matte_score_workspace_bytes(n, h, w):
+    return lib().vm_matte_score_workspace_bytes(n, h, w)
+
+
+def _score_plane(who, name, t, shape, dtypes):
+    """A contiguous torch tensor of ``shape`` and one of ``dtypes``, checked on the host (its device is checked last)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
+    if t.dtype not in dtypes:
+        raise TypeError("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: %s must be %s, got %s" % (who, name, list(shape), tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+
+
+def matte_score(pred, gt, trimap=None, prev=None, backward=None, out=None, grad_map=None, work=None):
+    """vm_matte_score: the sums behind SAD, MSE, gradient error, dtSSD and MESSDdt of ``pred`` against ``gt`` (each
+    [n,h,w], f32 or uint8 independently; an f32 value is clamped to [0,1], a uint8 is q / 255) -> f64 [n,8], row j =
+    [pixels of the region, sum |d|, sum d^2, sum gradient error, sum dt, sum me, pixels behind sum me, 0]
+    (include/vmatting.h; score_summary turns the rows into the figures).  ``trimap`` uint8 [n,h,w]: the region is where
+    it is neither 0 nor 255; None: every pixel.  ``prev`` = (prev_pred, prev_gt), [h,w] with the dtypes of pred and gt:
+    the frame before frame 0, for its temporal entries (None: they are 0).  ``backward`` f32 [n,h,w,2]: frame j's flow
+    into frame j - 1 (reader.read_flow layout, as estimate_flow returns it), for MESSDdt.  ``out`` f64 [n,8],
+    ``grad_map`` f32 [n,h,w] (receives the gradient error of every pixel), ``work`` a uint8 buffer of
+    matte_score_workspace_bytes(n, h, w): contiguous device tensors; out and work are allocated when None."""
+    who = "matte_score"
+    if not isinstance(pred, torch.Tensor):
+        raise TypeError("%s: pred must be a torch tensor, got %s" % (who, type(pred).__name__))
+    if pred.dim() != 3 or min(pred.shape) < 1:
+        raise ValueError("%s: pred must be [n,h,w], got %s" % (who, tuple(pred.shape)))
+    n, h, w = (int(v) for v in pred.shape)
+    mattes = tuple(_SCORE_DT)
+    _score_plane(who, "pred", pred, (n, h, w), mattes)
+    _score_plane(who, "gt", gt, (n, h, w), mattes)
+    if trimap is not None:
+        _score_plane(who, "trimap", trimap, (n, h, w), (torch.uint8,))
+    pp = pg = None
+    if prev is not None:
+        if not isinstance(prev, (tuple, list)) or len(prev) != 2:
+            raise TypeError("%s: prev must be the pair (prev_pred, prev_gt)" % who)
+        pp, pg = prev
+        _score_plane(who, "prev_pred", pp, (h, w), (pred.dtype,))
+        _score_plane(who, "prev_gt", pg, (h, w), (gt.dtype,))
+    if backward is not None:
+        _score_plane(who, "backward", backward, (n, h, w, 2), (torch.float32,))
+    if out is not None:
+        _score_plane(who, "out", out, (n, 8), (torch.float64,))
+    if grad_map is not None:
+        _score_plane(who, "grad_map", grad_map, (n, h, w), (torch.float32,))
+    for t in (pred, gt, trimap, pp, pg, backward, out, grad_map):
+        if t is not None:
+            _require_gpu(t)
+    if out is None:
+        out = torch.empty((n, 8), dtype=torch.float64, device=pred.device)
+    work = _flow_buffer(who, "work", work, matte_score_workspace_bytes(n, h, w), torch.uint8, pred.device)
+    check(lib().vm_matte_score(_ptr(pred), _SCORE_DT[pred.dtype], _ptr(gt), _SCORE_DT[gt.dtype], _ptr(trimap), _ptr(pp),
+                               _ptr(pg), _ptr(backward), n, h, w, _ptr(out), _ptr(grad_map), _ptr(work),
+                               stream_handle()), who)
+    return out
+
+
+SCORE_FIGURES = ("sad", "mse", "grad", "dtssd", "messddt")
+
+
+def score_summary(stats, first_has_prev=False, has_flow=False):
+    """The figures behind matte_score's rows, on the host (no GPU): ``stats`` f64 [n,8] (a numpy array or a tensor) ->
+    a dict of per-frame float64 arrays, "count" (pixels of the region), "sad" = sum |d|, "mse" = sum d^2 / count,
+    "grad" = the summed gradient error, "dtssd" = sqrt(sum dt / count), "messddt" = sum me / "taking_part", and under
+    "clip" the mean of each figure over the frames where it exists.  A figure that does not exist is NaN and left out
+    of its mean: every figure of a frame whose region is empty, dtssd and messddt of frame 0 unless ``first_has_prev``
+    (the call was given ``prev``), messddt without ``has_flow`` or where no pixel took part.  Published tables usually
+    quote SAD / 1000, MSE * 1000 and Grad / 1000."""
+    if isinstance(stats, torch.Tensor):
+        stats = stats.detach().cpu().numpy()
+    s = np.asarray(stats)
+    if s.dtype != np.float64:
+        raise TypeError("score_summary: stats must be float64, got %s" % s.dtype)
+    if s.ndim != 2 or s.shape[1] != 8:
+        raise ValueError("score_summary: stats must be [n,8], got %s" % (s.shape,))
+    n = s.shape[0]
+    count, part = s[:, 0].copy(), s[:, 6].copy()
+    exists = count > 0
+    temporal = exists.copy()
+    if n and not first_has_prev:
+        temporal[0] = False
+    flow = temporal & bool(has_flow) & (part > 0)
+    safe, safe_part = np.where(exists, count, 1.0), np.where(flow, part, 1.0)
+    nan = np.full(n, np.nan)
+    res = {"count": count, "taking_part": part,
+           "sad": np.where(exists, s[:, 1], nan), "mse": np.where(exists, s[:, 2] / safe, nan),
+           "grad": np.where(exists, s[:, 3], nan), "dtssd": np.where(temporal, np.sqrt(s[:, 4] / safe), nan),
+           "messddt": np.where(flow, s[:, 5] / safe_part, nan)}
+    res["clip"] = {k: float(res[k][~np.isnan(res[k])].mean()) if (~np.isnan(res[k])).any() else float("nan")
+                   for k in SCORE_FIGURES}
+    return res
+
+
 # ---------------------------------------------------------------- training step (train.py:288-343, config 5)
 
 def matting_loss_backward(pred, gt, raw_fg, in_bg, in_cmp, out=None):

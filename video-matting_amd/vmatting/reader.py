@@ -91,6 +91,36 @@ def replace_background(cmp, bg, alpha, new_bg):
     return _compose_frame(cmp, bg, alpha, new_bg, "over")
 
 
+def score_matte(pred, gt, trimap=None):
+    """The per-frame matting metrics of one matte against its ground truth: {"count": pixels of the region, "sad": sum
+    |pred - gt|, "mse": mean squared error, "grad": summed Gaussian-gradient error} over the trimap's unknown region
+    (bytes that are neither 0 nor 255; every pixel without a trimap).  pred, gt [h,w], each f32 or f64 in [0,1] (f64
+    is rounded to f32 first, values are clamped) or uint8 (q / 255); trimap uint8 [h,w] or None.  numpy in -> floats
+    out, through the vm_matte_score kernel (include/vmatting.h; published tables quote SAD / 1000, MSE * 1000 and
+    Grad / 1000).  A clip, and its temporal metrics, go through vmatting.MatteScorer."""
+    from vmatting import ops
+    planes = []
+    for name, a in (("pred", pred), ("gt", gt)):
+        a = np.asarray(a)
+        if a.dtype == np.float64:
+            a = a.astype(np.float32)
+        if a.dtype not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise TypeError("%s must be float32, float64 or uint8, got %s" % (name, a.dtype))
+        if a.ndim != 2 or a.size == 0 or a.shape != np.shape(pred):
+            raise ValueError("%s must be [h,w] like pred %s, got %s" % (name, np.shape(pred), a.shape))
+        planes.append(a)
+    if trimap is not None:
+        trimap = np.asarray(trimap)
+        if trimap.dtype != np.uint8:
+            raise TypeError("trimap must be uint8, got %s" % trimap.dtype)
+        if trimap.shape != planes[0].shape:
+            raise ValueError("trimap must be [h,w] = %s, got %s" % (planes[0].shape, trimap.shape))
+        planes.append(trimap)
+    dev = [torch.from_numpy(np.ascontiguousarray(a)[None]).cuda() for a in planes]
+    res = ops.score_summary(ops.matte_score(dev[0], dev[1], dev[2] if len(dev) == 3 else None))
+    return {k: float(res[k][0]) for k in ("count", "sad", "mse", "grad")}
+
+
 def read_fg_img(img_path):
     """reader.read_fg_img (reader.py:10-18) via PIL: returns (alpha in [0,1] float64, BGR uint8)."""
     from PIL import Image
