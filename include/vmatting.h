@@ -729,6 +729,36 @@ size_t vm_trimap_propagate_workspace_bytes(int h, int w, int grow);
 int vm_trimap_propagate(const uint8_t* prev, const float* flow, int h, int w, int grow, uint8_t* out, void* work,
                         void* stream);
 
+/* ---------------------------------------------------------------- trimaps from the background plate
+ * The background is a model input, so a trimap can be derived from the frame's difference to it instead of painted
+ * (the reference derives its trimaps from ground-truth mattes, data.trimap_from_matte: a certain core plus a narrow
+ * unknown band; no counterpart for inference).  trimap_from_plate(cmp, bg, lo, hi, r_bg, r_fg) = out, per frame, all
+ * integer:
+ *   cmp   uint8 [n,h,w,3] BGR; bg uint8 [nb,h,w,3], nb == n or nb == 1 (one static plate), as vm_frames_from_u8
+ *   d     d(x, y) = sum over c of (cmp_c - bg_c)^2, int32
+ *   D     D(x, y) = the sum of d over the 3 x 3 neighbourhood, coordinates clamped to the image (replicated border,
+ *         always 9 terms)
+ *   B0    D <= 9 lo^2;  F0: D >= 9 hi^2.  lo and hi are colour distances in levels, 0 <= lo < hi <= 442 (both bounds
+ *         fit int32; 3 * 255^2 < 442^2)
+ *   B     B(x, y) holds when every pixel of the (2 r_bg + 1)^2 window around it, clipped to the image, is in B0; F the
+ *         same with r_fg and F0.  Pixels outside the image do not erode.  Radii 0..32
+ *   out   uint8 [n,h,w]: 255 where F, 0 where B, 128 elsewhere (lo < hi: the two exclude each other); it must not
+ *         overlap cmp or bg
+ * What this is not: it has no shadow or exposure model (a shadow on the plate or a gain change is a difference like
+ * any other).  It cannot tell a translucent high-contrast pixel from an opaque one, so r_fg must exceed the width of
+ * the soft edge.  Foreground that matches the plate over an area wider than 2 r_bg + 1 is labelled background.
+ * tests/trimap_plate_ref.py restates the definition in numpy; the kernels match it byte for byte.
+ * Two launches for all n frames (csrc/trimap_plate.hip): the candidates B0 and F0 as bit rows into `work` (0.25 B per
+ * pixel), then the two erosions and the result bytes.
+ *   work  vm_trimap_from_plate_workspace_bytes(n, h, w) bytes, 16-byte aligned
+ * No allocation, no atomics and no synchronisation inside: the call can be captured in a graph.  VM_EINVAL for a NULL
+ * pointer, n, h or w < 1 (or n * h * w beyond 2^31 - 1), nb not 1 or n, lo / hi / a radius out of range or lo >= hi,
+ * out overlapping cmp or bg, or a misaligned work (checked before any HIP call); the size query returns 0 for such
+ * shapes. */
+size_t vm_trimap_from_plate_workspace_bytes(int n, int h, int w);
+int vm_trimap_from_plate(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int h, int w, int lo, int hi, int r_bg,
+                         int r_fg, uint8_t* out, void* work, void* stream);
+
 /* ---------------------------------------------------------------- matting metrics of a matte against ground truth
  * The per-frame metrics of Rhemann et al. (SAD, MSE, gradient error) over the trimap's unknown region and the temporal
  * metrics of Erofeev et al. (dtSSD, MESSDdt) as per-frame sums; the figures follow from the sums on the host (the

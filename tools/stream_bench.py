@@ -7,10 +7,13 @@ line and writes it under "stream_bench" in profiles/compose_stream.json.  The pr
 propagate``, at every size of ``--propagate-sizes``) measures vm_trimap_propagate alone for grow 0, 1 and 4 against its
 bytes-per-pixel model, the flow estimator's calls per frame, and FrameStream with per-frame trimaps, with
 trimap="propagate" on given flows and on estimated ones, interleaved in one process; it prints a third JSON line and
-writes profiles/trimap_propagate.json.
+writes profiles/trimap_propagate.json.  The auto section (``--sections auto``) measures vm_trimap_from_plate for one
+frame and for a chunk at radii (0, 0), the defaults and (32, 32) against its bytes model and against the same
+definition in torch ops (equal bytes asserted), and FrameStream(trimap="auto") beside per-frame trimaps, interleaved; it
+prints a JSON line and writes profiles/trimap_auto.json.
 
     python tools/stream_bench.py [--frames 64] [--chunk 8] [--height 1080] [--width 1920] [--reps 9]
-                                 [--sections ingest,compose,propagate] [--propagate-sizes 500x1200,1080x1920]
+                                 [--sections ingest,compose,propagate,auto] [--propagate-sizes 500x1200,1080x1920]
 
 Kernel times are hipEvent medians over ``--reps`` runs after a warm-up; every run of a kernel works on another of
 several buffer sets, so the 83 MB alpha of the quantise kernel does not sit in the 256 MB memory-side cache between
@@ -373,6 +376,135 @@ def propagate_section(a):
     print(line)
 
 
+AUTO_BYTES_PER_PIXEL = 6 + 1 + 0.5  # cmp and bg read, the trimap written, the bit rows written and read back
+
+
+def torch_plate(cmp, bg, lo, hi, r_bg, r_fg):
+    """vm_trimap_from_plate's definition in torch ops on the device.  d <= 3 * 255^2 and its box sum < 2^24, so f32
+    holds them exactly; max_pool2d pads with -inf, which is a window clipped to the image."""
+    F = torch.nn.functional
+    q = cmp.float() - bg.float()
+    d = (q * q).sum(-1)[:, None]
+    D = F.avg_pool2d(F.pad(d, (1, 1, 1, 1), mode="replicate"), 3, stride=1, divisor_override=1)
+    def erode(m, r):  # (the square window as a row pass and a column pass: 2 (2 r + 1) taps, not (2 r + 1)^2)
+        if r == 0:
+            return m
+        rows = F.max_pool2d(-m, (1, 2 * r + 1), stride=1, padding=(0, r))
+        return -F.max_pool2d(rows, (2 * r + 1, 1), stride=1, padding=(r, 0))
+    back = erode((D <= 9 * lo * lo).float(), r_bg) > 0
+    fore = erode((D >= 9 * hi * hi).float(), r_fg) > 0
+    out = torch.full(D.shape, 128, dtype=torch.uint8, device=cmp.device)
+    out[back] = 0
+    out[fore] = 255
+    return out[:, 0]
+
+
+def auto_section(a):
+    """vm_trimap_from_plate at [1 | chunk, height, width] for three radius pairs against its bytes model, the torch route
+    to the same bytes, and FrameStream(trimap="auto") beside trimap=True on the same frames, interleaved."""
+    from vmatting import FrameStream, ops, unet
+    from vmatting.weights import synthetic_vgg16
+    h, w, F = a.height, a.width, a.frames
+    hw = h * w
+    res = {"height": h, "width": w, "chunk": a.chunk, "frames": F, "reps": a.reps,
+           "device": torch.cuda.get_device_name(0), "hbm_peak_GBps": HBM_PEAK / 1e9,
+           "bytes_per_pixel": AUTO_BYTES_PER_PIXEL, "defaults": dict(ops.PLATE_DEFAULTS)}
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0)
+    o = ops.PLATE_DEFAULTS
+    radii = {"r0_0": (0, 0), "defaults": (o["r_bg"], o["r_fg"]), "r32_32": (32, 32)}
+
+    def frames(n, nsets):
+        """Plates of coarse blocks, and frames that equal them but for a little noise and a band of another colour: every
+        label occurs, in regions wider than the erosion windows."""
+        bg = torch.randint(0, 256, (nsets, n, (h + 63) // 64, (w + 63) // 64, 3), generator=g, device="cuda",
+                           dtype=torch.uint8).repeat_interleave(64, 2).repeat_interleave(64, 3)[:, :, :h, :w].contiguous()
+        cmp = bg ^ torch.randint(0, 4, bg.shape, generator=g, device="cuda", dtype=torch.uint8)
+        cmp[:, :, h // 4:3 * h // 4, w // 3:2 * w // 3] ^= 0x80
+        return cmp, bg
+
+    def kernels():
+        out = {}
+        for n in (1, a.chunk):
+            # enough buffer sets that one round of calls streams more than the 256 MB memory-side cache
+            nsets = max(a.sets, int(300e6 / (AUTO_BYTES_PER_PIXEL * n * hw)) + 1)
+            cmp, bg = frames(n, nsets)
+            outs = torch.empty((nsets, n, h, w), dtype=torch.uint8, device="cuda")
+            work = torch.empty(ops.trimap_from_plate_workspace_bytes(n, h, w), dtype=torch.uint8, device="cuda")
+            per = {"buffer_sets": nsets}
+            for name, (r_bg, r_fg) in radii.items():
+                call = lambda i, r_bg=r_bg, r_fg=r_fg: ops.trimap_from_plate(  # noqa: E731
+                    cmp[i], bg[i], o["lo"], o["hi"], r_bg, r_fg, out=outs[i], work=work)
+                ms = graph_ms([lambda i=i: call(i) for i in range(nsets)], a.reps, calls=200)
+                per[name] = dict(rate(n * hw * AUTO_BYTES_PER_PIXEL, ms), us=round(ms * 1e3, 2))
+                want = torch_plate(cmp[0], bg[0], o["lo"], o["hi"], r_bg, r_fg)
+                assert torch.equal(call(0), want), (n, name)  # the same bytes, so the same work is compared
+                per[name]["label_shares"] = [round(float((want == v).float().mean()), 3) for v in (0, 128, 255)]
+                ms_t = event_ms([lambda i=i: torch_plate(cmp[i], bg[i], o["lo"], o["hi"], r_bg, r_fg)
+                                 for i in range(min(nsets, 3))], a.reps)
+                per[name]["torch_route_ms"] = round(ms_t, 4)
+                per[name]["speedup_over_torch"] = round(ms_t / ms, 1)
+            # one static plate for all n frames
+            ms = graph_ms([lambda i=i: ops.trimap_from_plate(cmp[i], bg[i, 0], out=outs[i], work=work)
+                           for i in range(nsets)], a.reps, calls=200)
+            per["defaults_static_bg"] = dict(rate(n * hw * (AUTO_BYTES_PER_PIXEL - 3) + hw * 3, ms), us=round(ms * 1e3, 2))
+            out["n%d" % n] = per
+            del cmp, bg, outs, work
+            torch.cuda.empty_cache()
+        # the HBM yardstick on this box: a torch copy of 265 MB (tools/membw.py's "copy")
+        m = 1080 * 1920 * 64
+        x, y = torch.empty(m, dtype=torch.bfloat16, device="cuda"), torch.empty(m, dtype=torch.bfloat16, device="cuda")
+        out["torch_copy_265MB"] = rate(4 * m, event_ms([lambda: y.copy_(x)], a.reps))
+        return out
+    res["kernels"] = step("auto kernels", a.step_limit, kernels)
+    torch.cuda.empty_cache()
+
+    np.random.seed(0)
+    model = unet.UNetVideo(synthetic_vgg16(0), dtype="bf16", device="cuda").prepare()
+
+    def streamed():
+        n = a.chunk
+        k = min(F, 2 * n)  # two distinct chunks of host frames, cycled (the source hands out views of them)
+        cmp, bg = (t[0].cpu().numpy() for t in frames(k, 1))
+        tri = ops.trimap_from_plate(torch.from_numpy(cmp).cuda(), torch.from_numpy(bg).cuda()).cpu().numpy()
+        torch.cuda.empty_cache()
+
+        def source(mode):
+            for i in range(0, F, n):
+                m, s = min(n, F - i), i % k
+                yield cmp[s:s + m], bg[s:s + m], (tri[s:s + m] if mode == "per_frame" else None)
+        kw = dict(chunk=n, depth=2, out="u8")
+        streams = {"per_frame": FrameStream(model, h, w, **kw), "auto": FrameStream(model, h, w, trimap="auto", **kw)}
+
+        def run(mode):
+            t0 = time.perf_counter()
+            tot = sum(m.shape[0] for m in streams[mode].run(source(mode)))
+            torch.cuda.synchronize()
+            assert tot == F
+            return (time.perf_counter() - t0) * 1e3
+        times = {mode: [] for mode in streams}
+        for i in range(1 + max(3, a.reps // 2)):  # interleaved; round 0 warms up (and captures the graphs)
+            for mode in streams:
+                ms = run(mode)
+                if i:
+                    times[mode].append(ms)
+        out = {}
+        for mode, t in times.items():
+            ms = statistics.median(t)
+            out["frame_stream_bf16_trimap_" + mode] = {
+                "ms_per_frame": round(ms / F, 3), "frames_per_s": round(F / ms * 1e3, 1),
+                "min_ms_per_frame": round(min(t) / F, 3), "max_ms_per_frame": round(max(t) / F, 3)}
+        out["auto_adds_ms_per_frame"] = round(out["frame_stream_bf16_trimap_auto"]["ms_per_frame"] -
+                                              out["frame_stream_bf16_trimap_per_frame"]["ms_per_frame"], 3)
+        return out
+    res["streams"] = step("auto streams", a.step_limit, streamed)
+    line = json.dumps(res)
+    os.makedirs(os.path.dirname(a.auto_out), exist_ok=True)
+    with open(a.auto_out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
@@ -386,11 +518,12 @@ def main():
     ap.add_argument("--compose-out", default=os.path.join(REPO, "profiles", "compose_stream.json"))
     ap.add_argument("--propagate-out", default=os.path.join(REPO, "profiles", "trimap_propagate.json"))
     ap.add_argument("--propagate-sizes", default="500x1200,1080x1920", help="comma-separated HxW of the propagate section")
-    ap.add_argument("--sections", default="ingest,compose", help="comma-separated: ingest, compose, propagate")
+    ap.add_argument("--auto-out", default=os.path.join(REPO, "profiles", "trimap_auto.json"))
+    ap.add_argument("--sections", default="ingest,compose", help="comma-separated: ingest, compose, propagate, auto")
     a = ap.parse_args()
     sections = set(a.sections.split(","))
-    if not sections or sections - {"ingest", "compose", "propagate"}:
-        raise SystemExit("stream_bench: --sections takes ingest, compose and / or propagate, got %r" % a.sections)
+    if not sections or sections - {"ingest", "compose", "propagate", "auto"}:
+        raise SystemExit("stream_bench: --sections takes ingest, compose, propagate and / or auto, got %r" % a.sections)
     if not torch.cuda.is_available():
         raise SystemExit("stream_bench needs a ROCm GPU")
     if "ingest" in sections:
@@ -401,6 +534,9 @@ def main():
         torch.cuda.empty_cache()
     if "propagate" in sections:
         propagate_section(a)
+        torch.cuda.empty_cache()
+    if "auto" in sections:
+        auto_section(a)
 
 
 def ingest_section(a):

@@ -1181,6 +1181,57 @@ def trimap_propagate(prev, flow, grow=1, out=None, work=None):
     return out.view(h, w)
 
 
+# ---------------------------------------------------------------- trimaps from the background plate
+
+# colour distances in levels and erosion radii in pixels; untuned on real footage
+PLATE_DEFAULTS = {"lo": 16, "hi": 48, "r_bg": 4, "r_fg": 8}
+PLATE_LEVEL_MAX, PLATE_RADIUS_MAX = 442, 32
+
+
+def check_plate_options(who, lo, hi, r_bg, r_fg):
+    """The options of vm_trimap_from_plate as it checks them, on the host: integers with 0 <= lo < hi <= 442 and radii
+    in 0..32 -> (lo, hi, r_bg, r_fg)."""
+    for name, v in (("lo", lo), ("hi", hi), ("r_bg", r_bg), ("r_fg", r_fg)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError("%s: %s must be an integer, got %r" % (who, name, v))
+    if not 0 <= lo < hi <= PLATE_LEVEL_MAX:
+        raise ValueError("%s: 0 <= lo < hi <= %d expected, got lo %d, hi %d" % (who, PLATE_LEVEL_MAX, lo, hi))
+    for name, v in (("r_bg", r_bg), ("r_fg", r_fg)):
+        if not 0 <= v <= PLATE_RADIUS_MAX:
+            raise ValueError("%s: %s must be in 0..%d, got %d" % (who, name, PLATE_RADIUS_MAX, v))
+    return int(lo), int(hi), int(r_bg), int(r_fg)
+
+
+def trimap_from_plate_workspace_bytes(n, h, w):
+    return lib().vm_trimap_from_plate_workspace_bytes(n, h, w)
+
+
+def trimap_from_plate(cmp, bg, lo=PLATE_DEFAULTS["lo"], hi=PLATE_DEFAULTS["hi"], r_bg=PLATE_DEFAULTS["r_bg"],
+                      r_fg=PLATE_DEFAULTS["r_fg"], out=None, work=None):
+    """vm_trimap_from_plate: trimaps from the frames' difference to the background.  cmp u8 [n,h,w,3] BGR, bg u8
+    [n,h,w,3] or one static plate [h,w,3] / [1,h,w,3] -> uint8 [n,h,w]: 0 where the 3x3 box sum of the squared colour
+    distance stays within 9 lo^2 over a (2 r_bg + 1)^2 window, 255 where it reaches 9 hi^2 over a (2 r_fg + 1)^2 window,
+    128 elsewhere (include/vmatting.h).  ``out``: a contiguous uint8 [n,h,w] device tensor; ``work``: a uint8 device
+    buffer of trimap_from_plate_workspace_bytes(n, h, w); both are allocated when None."""
+    who = "trimap_from_plate"
+    for name, t in (("cmp", cmp), ("bg", bg)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
+    n, h, w, nb = _check_u8_frames(cmp, bg, None)
+    lo, hi, r_bg, r_fg = check_plate_options(who, lo, hi, r_bg, r_fg)
+    for name, t in (("cmp", cmp), ("bg", bg)):
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (who, name))
+        _require_gpu(t)
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, h, w)):
+        raise ValueError("%s: out must be [n,h,w] = %s, got %s" % (who, (n, h, w), tuple(getattr(out, "shape", ()))))
+    out = _flow_buffer(who, "out", out, n * h * w, torch.uint8, cmp.device)
+    work = _flow_buffer(who, "work", work, trimap_from_plate_workspace_bytes(n, h, w), torch.uint8, cmp.device)
+    check(lib().vm_trimap_from_plate(_ptr(cmp), _ptr(bg), nb, n, h, w, lo, hi, r_bg, r_fg, _ptr(out), _ptr(work),
+                                     stream_handle()), who)
+    return out.view(n, h, w)
+
+
 # ---------------------------------------------------------------- matting metrics against ground truth
 
 _SCORE_DT = {torch.float32: _lib.VM_F32, torch.uint8: _lib.VM_U8}

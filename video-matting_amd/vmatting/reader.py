@@ -121,6 +121,35 @@ def score_matte(pred, gt, trimap=None):
     return {k: float(res[k][0]) for k in ("count", "sad", "mse", "grad")}
 
 
+def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None):
+    """The trimap of a frame from its difference to the background plate: what FrameStream(trimap="auto") feeds the
+    model, and the trimap of a clip's first frame for ClipStream's alpha0.  cmp_u8 uint8 BGR, one frame [H,W,3] or a
+    stack [N,H,W,3]; bg_u8 uint8 [H,W,3] (one plate) or, with a stack, [N,H,W,3] -> uint8 [H,W] or [N,H,W]: 0 where the
+    frame equals the plate within ``lo`` levels over a (2 r_bg + 1)^2 window, 255 where it differs by ``hi`` or more
+    over a (2 r_fg + 1)^2 window, 128 elsewhere (ops.trimap_from_plate, include/vmatting.h; None: ops.PLATE_DEFAULTS,
+    which are untuned).  No shadow or exposure model.  numpy arrays return numpy, device tensors stay on the device."""
+    from vmatting import ops
+    who = "trimap_from_plate"
+    if isinstance(cmp_u8, torch.Tensor) != isinstance(bg_u8, torch.Tensor):
+        raise TypeError("%s: cmp and bg are both numpy arrays or both torch tensors" % who)
+    given = {"lo": lo, "hi": hi, "r_bg": r_bg, "r_fg": r_fg}
+    opts = dict(ops.PLATE_DEFAULTS, **{k: v for k, v in given.items() if v is not None})
+    ops.check_plate_options(who, **opts)
+    device = isinstance(cmp_u8, torch.Tensor)
+    if not device:
+        cmp_u8, bg_u8 = np.ascontiguousarray(cmp_u8), np.ascontiguousarray(bg_u8)
+    single = len(cmp_u8.shape) == 3
+    cmp = cmp_u8[None] if single else cmp_u8
+    if single and len(bg_u8.shape) != 3:
+        raise ValueError("%s: one [H,W,3] frame takes one [H,W,3] plate, got %s" % (who, tuple(bg_u8.shape)))
+    ops._check_u8_frames(cmp, bg_u8, None)
+    if device:
+        out = ops.trimap_from_plate(cmp.contiguous(), bg_u8.contiguous(), **opts)
+    else:
+        out = ops.trimap_from_plate(torch.from_numpy(cmp).cuda(), torch.from_numpy(bg_u8).cuda(), **opts).cpu().numpy()
+    return out[0] if single else out
+
+
 def read_fg_img(img_path):
     """reader.read_fg_img (reader.py:10-18) via PIL: returns (alpha in [0,1] float64, BGR uint8)."""
     from PIL import Image

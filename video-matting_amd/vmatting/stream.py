@@ -18,6 +18,9 @@ subtraction rounded to f32 once), bit for bit, then quantised.
 the chunk's chain starts with the recurrence tri[j] = ops.trimap_propagate(tri[j-1], backward[j], grow).  It depends on
 the frames only, never on the model's output, so the forward stays chunked.
 
+``trimap="auto"``: the user has no trimap at all.  The chunk's chain starts with ops.trimap_from_plate on the uploaded
+frames and the plate; nothing is kept between chunks.
+
 This is one process's share of a clip; sharding a clip across ranks stays video.shard's job.
 """
 
@@ -30,6 +33,7 @@ from .pipeline import PER_FRAME, Slot, SlotPipeline, check_new_bg, check_out, ch
 from .split6 import rerun_x6
 
 PROPAGATE = "propagate"
+AUTO = "auto"
 FLOW_MODES = ("given", "estimate")
 
 
@@ -43,12 +47,12 @@ class _Slot(Slot):
         given = fs.propagate and not fs.estimate
         super().__init__(fs.device, (("cmp", (n, h, w, 3), u8),
                                      ("bg", (n, h, w, 3) if fs.static_bg is None else None, u8),
-                                     ("tri", (n, h, w) if fs.trimap and not fs.propagate else None, u8),
+                                     ("tri", (n, h, w) if fs.trimap and not (fs.propagate or fs.auto) else None, u8),
                                      ("key", (1, h, w) if fs.propagate else None, u8),
                                      ("bw", (n, h, w, 2) if given else None, torch.float32),
                                      ("nw", (n, h, w, 3) if fs.new_bg is PER_FRAME else None, u8)),
                          n, h, w, fs.out, flag=fs.model.split_mode == "f16x3")  # f16x3: this slot's range flag
-        if fs.propagate:  # the chunk's trimaps are made on the device: no pinned twin, nothing uploaded
+        if fs.propagate or fs.auto:  # the chunk's trimaps are made on the device: no pinned twin, nothing uploaded
             self.d_tri = torch.zeros((n, h, w), dtype=u8, device=fs.device)
             if fs.estimate:
                 self.d_bw = torch.zeros((n, h, w, 2), dtype=torch.float32, device=fs.device)
@@ -87,23 +91,40 @@ class FrameStream(SlotPipeline):
     of ``trimap=True`` fed with these trimaps, bit for bit.  ``last_trimap()`` returns the last frame's trimap after a
     run: inspect its drift to place the next key.
 
+    ``trimap="auto"`` (a 7-channel model): no trimap is supplied at all.  Source items are the ordinary
+    ``(cmp, bg, None)`` (and new_bg last with "per_frame"), and every frame's trimap is
+    ops.trimap_from_plate(cmp, bg, **auto_options) on the device: background where the frame equals the plate, foreground
+    where it clearly differs, unknown in between (include/vmatting.h; no shadow or exposure model).  ``auto_options``: a
+    dict over ops.PLATE_DEFAULTS (lo, hi, r_bg, r_fg).  The mattes are those of ``trimap=True`` fed with these trimaps,
+    bit for bit; reader.trimap_from_plate shows them.
+
     If the source raises, or yields a wrong shape, dtype or k, the chunks already taken are finished and yielded, the
     streams are synchronised, and the exception then propagates; the object can run again."""
 
     def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True, new_bg=None,
-                 flow=None, flow_options=None, grow=1):
+                 flow=None, flow_options=None, grow=1, auto_options=None):
         h, w, chunk, depth = int(h), int(w), int(chunk), int(depth)
         if h < 1 or w < 1 or chunk < 1 or depth < 1:
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
                              (h, w, chunk, depth))
         check_out("FrameStream", out)
-        self.propagate = isinstance(trimap, str)
-        if self.propagate and trimap != PROPAGATE:
-            raise ValueError("FrameStream: trimap must be True, False or %r, got %r" % (PROPAGATE, trimap))
+        if isinstance(trimap, str) and trimap not in (PROPAGATE, AUTO):
+            raise ValueError("FrameStream: trimap must be True, False, %r or %r, got %r" % (PROPAGATE, AUTO, trimap))
+        self.propagate = isinstance(trimap, str) and trimap == PROPAGATE
+        self.auto = isinstance(trimap, str) and trimap == AUTO
         if (7 if trimap else 6) != model.IN_CH:
             raise ValueError("FrameStream: %s takes %d channels, so trimap must be %s" %
                              (type(model).__name__, model.IN_CH,
-                              "True or %r" % PROPAGATE if model.IN_CH == 7 else False))
+                              "True, %r or %r" % (PROPAGATE, AUTO) if model.IN_CH == 7 else False))
+        if auto_options is not None and not self.auto:
+            raise ValueError("FrameStream: auto_options go with trimap=%r" % AUTO)
+        if self.auto:
+            opts = dict(ops.PLATE_DEFAULTS)
+            for k, v in dict(auto_options or {}).items():
+                if k not in opts:
+                    raise ValueError("FrameStream: auto_options takes %s, got %r" % (sorted(opts), k))
+                opts[k] = v
+            self.auto_options = dict(zip(("lo", "hi", "r_bg", "r_fg"), ops.check_plate_options("FrameStream", **opts)))
         if not self.propagate and (flow is not None or flow_options is not None):
             raise ValueError("FrameStream: flow and flow_options go with trimap=%r" % PROPAGATE)
         self.grow = ops.check_grow("FrameStream", grow)
@@ -143,6 +164,9 @@ class FrameStream(SlotPipeline):
             raise ValueError("FrameStream: the source yields (cmp, bg, trimap%s)" %
                              (", new_bg) with new_bg='per_frame'" if per_frame else ") triples"))
         cmp, bg, tri = item[:3]
+        if self.auto and tri is not None:
+            raise ValueError("FrameStream: with trimap=%r the trimaps are made from the plate: the item's trimap is "
+                             "None" % AUTO)
         k, nw = self._check_frames(cmp, bg, tri, item[3] if per_frame else None)
         return (cmp, bg, tri, k, nw) if per_frame else (cmp, bg, tri, k)
 
@@ -153,7 +177,7 @@ class FrameStream(SlotPipeline):
             raise TypeError("FrameStream: cmp must be a numpy array, got %s" % type(cmp).__name__)
         if (bg is None) != (self.static_bg is not None):
             raise ValueError("FrameStream: bg is None exactly when a static_bg was given")
-        if not self.propagate and (tri is None) == self.trimap:
+        if not (self.propagate or self.auto) and (tri is None) == self.trimap:
             raise ValueError("FrameStream: trimap is None exactly when trimap=False")
         for name, a in (("bg", bg), ("trimap", tri)):
             if a is not None and not isinstance(a, np.ndarray):
@@ -207,6 +231,9 @@ class FrameStream(SlotPipeline):
             self._new_plate = torch.from_numpy(self.new_bg).to(self.device)
         if self.propagate:
             self._setup_propagate()
+        if self.auto:  # one workspace for every slot: the chains run one after another on the compute stream
+            self._auto_work = torch.zeros(ops.trimap_from_plate_workspace_bytes(self.chunk, self.h, self.w),
+                                          dtype=torch.uint8, device=self.device)
         self._slots = [_Slot(self) for _ in range(self.depth)]
         torch.cuda.synchronize(self.device)  # the plates and the zeroed pad channels, before another stream reads them
         if self.propagate and self.graph:
@@ -268,10 +295,12 @@ class FrameStream(SlotPipeline):
 
     def _chain(self, s, k, keyed=False):
         """Ingest -> forward -> quantise | compose -> download of the slot's first k frames, on the current stream;
-        with trimap="propagate" the frames' trimaps first."""
+        with trimap="propagate" or "auto" the frames' trimaps first."""
         bg = self._plate if self._plate is not None else s.d_bg[:k]
         if self.propagate:
             self._trimaps(s, k, keyed)
+        if self.auto:
+            ops.trimap_from_plate(s.d_cmp[:k], bg, out=s.d_tri[:k], work=self._auto_work, **self.auto_options)
         ops.frames_from_u8(s.d_cmp[:k], bg, None if s.d_tri is None else s.d_tri[:k], out=s.frames[:k])
         self.model.forward(s.frames[:k], out=s.alpha[:k], overflow=s.flag)
         self._download(s, k)
@@ -286,6 +315,8 @@ class FrameStream(SlotPipeline):
         def pre():
             if keyed is not None:
                 self._trimaps(s, self.chunk, keyed)
+            if self.auto:
+                ops.trimap_from_plate(s.d_cmp, bg, out=s.d_tri, work=self._auto_work, **self.auto_options)
             ops.frames_from_u8(s.d_cmp, bg, s.d_tri, out=s.frames)
 
         graph = self.model.capture(s.frames, static=True, out=s.alpha, overflow=s.flag, pre=pre,
