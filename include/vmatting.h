@@ -759,6 +759,32 @@ size_t vm_trimap_from_plate_workspace_bytes(int n, int h, int w);
 int vm_trimap_from_plate(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int h, int w, int lo, int hi, int r_bg,
                          int r_fg, uint8_t* out, void* work, void* stream);
 
+/* ---------------------------------------------------------------- the background plate from the clip itself
+ * Every model takes the clean background plate; a shot without one can estimate it, if the camera is locked off and the
+ * subject moves, as the per-pixel temporal median of a sample of its frames (the reference has no counterpart: its
+ * backgrounds are given).  plate_from_samples(samples) = (plate, spread), all integer:
+ *   samples  uint8 [n,h,w,3], contiguous, 1 <= n <= VM_PLATE_MAX_SAMPLES
+ *   sorted   for every byte position p of a frame (h * w * 3 of them) s_0 <= ... <= s_{n-1}: the n sample bytes at p
+ *   plate    uint8 [h,w,3]: plate[p] = s_m, m = (n - 1) / 2 (integer division).  The lower median, per channel, nothing
+ *            averaged: every output byte occurred in the samples.  np.sort(samples, 0)[m]
+ *   spread   uint8 [h,w] or NULL: spread[y,x] = max over the pixel's three bytes of (s_hi - s_lo), lo = (n - 1) / 4,
+ *            hi = n - 1 - lo: the interquantile range, large where the subject covered the pixel in a good share of the
+ *            samples or where the shot is noisy, that is, where the plate is not to be trusted
+ *   n == 1   plate = samples[0], spread = 0
+ * Consequences: a pixel that the subject covers in at most (n - 1) / 2 samples and that shows one value in all others
+ * gets that value, whatever covered it; covered in at most (n - 1) / 4 samples, its spread is 0 as well.
+ * What this is not: it needs a locked-off camera; a pixel covered in more than half the samples gets the subject's
+ * colour (spread shows it); there is no exposure or flicker compensation.
+ * tests/plate_ref.py restates the definition in numpy; the kernel matches it byte for byte.
+ * One launch (csrc/plate.hip): a thread per dword of the frame, the n samples of its 4 bytes in registers through a
+ * sorting network.  samples, plate and spread may sit at any byte address.  No byte outside plate[0 : h*w*3] and
+ * spread[0 : h*w] is written.
+ * No workspace, no allocation, no atomics and no synchronisation inside: the call can be captured in a graph.
+ * VM_EINVAL for a NULL samples or plate, n outside 1..64, h or w < 1, n * h * w * 3 beyond 2^31 - 1, or plate / spread
+ * overlapping samples or each other (checked before any HIP call). */
+#define VM_PLATE_MAX_SAMPLES 64
+int vm_plate_from_samples(const uint8_t* samples, int n, int h, int w, uint8_t* plate, uint8_t* spread, void* stream);
+
 /* ---------------------------------------------------------------- matting metrics of a matte against ground truth
  * The per-frame metrics of Rhemann et al. (SAD, MSE, gradient error) over the trimap's unknown region and the temporal
  * metrics of Erofeev et al. (dtSSD, MESSDdt) as per-frame sums; the figures follow from the sums on the host (the

@@ -10,6 +10,8 @@ from .params import VGG_MEAN  # noqa: F401
 from .stream import FrameStream  # noqa: F401
 from .clip import ClipStream  # noqa: F401
 from .score import MatteScorer  # noqa: F401
+from .plate import PlateEstimator, SampleSchedule  # noqa: F401
 
 __all__ = ["unet", "unet_simple", "small", "refine", "flow", "reader", "tps", "augmentation", "loader", "parallel", "ops",
-           "weights", "video", "stream", "FrameStream", "clip", "ClipStream", "score", "MatteScorer"]
+           "weights", "video", "stream", "FrameStream", "clip", "ClipStream", "score", "MatteScorer", "plate",
+           "PlateEstimator", "SampleSchedule"]

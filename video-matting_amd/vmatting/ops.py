@@ -1232,6 +1232,51 @@ def trimap_from_plate(cmp, bg, lo=PLATE_DEFAULTS["lo"], hi=PLATE_DEFAULTS["hi"],
     return out.view(n, h, w)
 
 
+# ---------------------------------------------------------------- the background plate from the clip itself
+
+PLATE_MAX_SAMPLES = 64
+
+
+def plate_from_samples(samples, plate=None, spread=None, want_spread=True):
+    """vm_plate_from_samples: the background plate of a locked-off shot from n of its frames.  samples u8 [n,h,w,3],
+    contiguous, 1 <= n <= 64 -> (plate u8 [h,w,3], spread u8 [h,w]): per byte the lower median over the samples
+    (np.sort(samples, 0)[(n - 1) // 2]), and per pixel the largest interquantile range of its three bytes, which is
+    large where the plate is not to be trusted (include/vmatting.h).  ``plate`` / ``spread``: contiguous uint8 device
+    tensors of those shapes, allocated when None; with ``want_spread`` False no spread is computed and (plate, None)
+    returned."""
+    who = "plate_from_samples"
+    for name, t in (("samples", samples), ("plate", plate), ("spread", spread)):
+        if t is None and name != "samples":
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
+        if t.dtype != torch.uint8:
+            raise TypeError("%s: %s must be uint8, got %s" % (who, name, t.dtype))
+    if samples.dim() != 4 or samples.shape[3] != 3 or min(samples.shape) < 1:
+        raise ValueError("%s: samples must be [n,h,w,3] BGR, got %s" % (who, tuple(samples.shape)))
+    n, h, w, _ = (int(v) for v in samples.shape)
+    if n > PLATE_MAX_SAMPLES:
+        raise ValueError("%s: at most %d samples, got %d" % (who, PLATE_MAX_SAMPLES, n))
+    if spread is not None and not want_spread:
+        raise ValueError("%s: a spread buffer although want_spread is False" % who)
+    for name, t, shape in (("samples", samples, (n, h, w, 3)), ("plate", plate, (h, w, 3)), ("spread", spread, (h, w))):
+        if t is None:
+            continue
+        if tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be %s, got %s" % (who, name, shape, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (who, name))
+    for t in (samples, plate, spread):
+        if t is not None:
+            _require_gpu(t)
+    if plate is None:
+        plate = torch.empty((h, w, 3), dtype=torch.uint8, device=samples.device)
+    if spread is None and want_spread:
+        spread = torch.empty((h, w), dtype=torch.uint8, device=samples.device)
+    check(lib().vm_plate_from_samples(_ptr(samples), n, h, w, _ptr(plate), _ptr(spread), stream_handle()), who)
+    return plate, spread
+
+
 # ---------------------------------------------------------------- matting metrics against ground truth
 
 _SCORE_DT = {torch.float32: _lib.VM_F32, torch.uint8: _lib.VM_U8}

@@ -150,6 +150,29 @@ def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None):
     return out[0] if single else out
 
 
+def plate_from_clip(frames_u8, capacity=64, every=1):
+    """The background plate of a locked-off clip estimated from its own frames, for a shot without a clean plate:
+    frames_u8 uint8 BGR [N,H,W,3] -> (plate uint8 [H,W,3], spread uint8 [H,W]).  Up to ``capacity`` (even, 2..64) of
+    every ``every``-th frame, spread evenly over the clip (plate.SampleSchedule), and per byte their lower median;
+    ``spread`` is the per-pixel interquantile range, large where the subject stood for a good share of the clip and the
+    plate is not to be trusted (ops.plate_from_samples, include/vmatting.h).  No exposure or flicker compensation.
+    numpy arrays return numpy, device tensors stay on the device."""
+    from vmatting.plate import PlateEstimator
+    who = "plate_from_clip"
+    if not isinstance(frames_u8, (np.ndarray, torch.Tensor)):
+        raise TypeError("%s: frames must be a numpy array or a device tensor, got %s" % (who, type(frames_u8).__name__))
+    if str(frames_u8.dtype).split(".")[-1] != "uint8":
+        raise TypeError("%s: frames must be uint8, got %s" % (who, frames_u8.dtype))
+    shape = tuple(frames_u8.shape)
+    if len(shape) != 4 or shape[3] != 3 or min(shape) < 1:
+        raise ValueError("%s: frames must be [N,H,W,3] BGR, got %s" % (who, shape))
+    est = PlateEstimator(shape[1], shape[2], capacity, every)
+    plate, spread = est.add(frames_u8).result()
+    if isinstance(frames_u8, torch.Tensor):
+        return plate, spread
+    return plate.cpu().numpy(), spread.cpu().numpy()
+
+
 def read_fg_img(img_path):
     """reader.read_fg_img (reader.py:10-18) via PIL: returns (alpha in [0,1] float64, BGR uint8)."""
     from PIL import Image
