@@ -759,6 +759,42 @@ size_t vm_trimap_from_plate_workspace_bytes(int n, int h, int w);
 int vm_trimap_from_plate(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int h, int w, int lo, int hi, int r_bg,
                          int r_fg, uint8_t* out, void* work, void* stream);
 
+/* ---------------------------------------------------------------- connected components, and enclosed background
+ * components_label(mask, value, connectivity) = labels, per frame:
+ *   mask     uint8 [n,h,w] at any byte address; a pixel is set iff its byte equals value (0..255)
+ *   labels   int32 [n,h,w], 4-byte aligned, not overlapping mask: for a set pixel the smallest row-major index y w + x
+ *            within its own frame among the pixels of its 4- or 8-connected component, -1 for every other pixel
+ * The labels array is the working storage (no workspace).  A union-find with parents that only ever decrease
+ * (csrc/components.hip states the invariant): the result is canonical, it does not depend on the order of the atomics.
+ * Three launches (two where the frame is one 64 x 32 tile), no allocation, no synchronisation, no host read-back: the
+ * call can be captured in a graph.
+ *
+ * trimap_fill_enclosed(trimap, max_area) = out, per frame, all integer: the automatic trimap's background label is a
+ * hard claim, and foreground that matches the plate over a wide area gets it; such a hole does not reach the frame.
+ *   Z        the pixels whose byte is 0, and their 4-connected components (4, so that the background does not leak
+ *            through a diagonal gap of an 8-connected subject)
+ *   enclosed a component none of whose pixels has y in {0, h - 1} or x in {0, w - 1}
+ *   out      uint8 [n,h,w]: 128 on the pixels of every enclosed component of at most max_area pixels (max_area == 0: of
+ *            any area); everywhere else the input byte, whatever it is (only == 0 is ever tested).  h < 3 or w < 3:
+ *            nothing is enclosed, the call is a copy
+ *   out == trimap (the same pointer) fills in place; any other overlap of out, trimap and work is refused.  trimap and
+ *            out may sit at any byte address
+ *   work     vm_trimap_fill_enclosed_workspace_bytes(n, h, w) = 8 n h w bytes, 16-byte aligned: the labels, and an
+ *            int32 per pixel that holds the component's border flag and area at its root.  The call initialises what
+ *            it reads: the workspace's contents before it do not matter
+ * What this is not: a hole that reaches the frame's border is not filled, and a legitimate enclosed gap (between arm
+ * and body) becomes unknown as well.  tests/trimap_fill_ref.py restates both definitions in numpy by a breadth-first
+ * flood; the kernels match it exactly.
+ * Four launches (one copy for h < 3 or w < 3), the area sums only with max_area > 0.  VM_EINVAL for a NULL pointer, n, h
+ * or w < 1 (or n * h * w beyond 2^31 - 1), value outside 0..255, connectivity other than 4 or 8, max_area < 0, a
+ * misaligned labels or work, or a forbidden overlap (checked before any HIP call); the size query returns 0 for such
+ * shapes. */
+int vm_components_label(const uint8_t* mask, int n, int h, int w, int value, int connectivity, int32_t* labels,
+                        void* stream);
+size_t vm_trimap_fill_enclosed_workspace_bytes(int n, int h, int w);
+int vm_trimap_fill_enclosed(const uint8_t* trimap, int n, int h, int w, int max_area, uint8_t* out, void* work,
+                            void* stream);
+
 /* ---------------------------------------------------------------- the background plate from the clip itself
  * Every model takes the clean background plate; a shot without one can estimate it, if the camera is locked off and the
  * subject moves, as the per-pixel temporal median of a sample of its frames (the reference has no counterpart: its

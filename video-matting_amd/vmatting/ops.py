@@ -1232,6 +1232,80 @@ def trimap_from_plate(cmp, bg, lo=PLATE_DEFAULTS["lo"], hi=PLATE_DEFAULTS["hi"],
     return out.view(n, h, w)
 
 
+# ---------------------------------------------------------------- connected components, and enclosed background
+
+def _check_u8_stack(who, name, t):
+    """A contiguous uint8 [n,h,w] device tensor -> (n, h, w)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
+    if t.dtype != torch.uint8:
+        raise TypeError("%s: %s must be uint8, got %s" % (who, name, t.dtype))
+    if t.dim() != 3 or min(t.shape) < 1:
+        raise ValueError("%s: %s must be [n,h,w], got %s" % (who, name, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+    _require_gpu(t)
+    return tuple(int(v) for v in t.shape)
+
+
+def label_components(mask, value=0, connectivity=4, out=None):
+    """vm_components_label: the connected components of the pixels of ``mask`` (uint8 [n,h,w]) whose byte equals
+    ``value`` -> int32 [n,h,w]: for such a pixel the smallest row-major index y * w + x, within its own frame, of its 4-
+    or 8-connected component; -1 for every other pixel (include/vmatting.h).  ``out``: a contiguous int32 [n,h,w] device
+    tensor, allocated when None."""
+    who = "label_components"
+    n, h, w = _check_u8_stack(who, "mask", mask)
+    for name, v in (("value", value), ("connectivity", connectivity)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError("%s: %s must be an integer, got %r" % (who, name, v))
+    if not 0 <= value <= 255:
+        raise ValueError("%s: value must be in 0..255, got %d" % (who, value))
+    if connectivity not in (4, 8):
+        raise ValueError("%s: connectivity must be 4 or 8, got %d" % (who, connectivity))
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, h, w)):
+        raise ValueError("%s: out must be [n,h,w] = %s, got %s" % (who, (n, h, w), tuple(getattr(out, "shape", ()))))
+    out = _flow_buffer(who, "out", out, n * h * w, torch.int32, mask.device)
+    check(lib().vm_components_label(_ptr(mask), n, h, w, int(value), int(connectivity), _ptr(out), stream_handle()), who)
+    return out.view(n, h, w)
+
+
+def check_fill(who, fill):
+    """The hole-filling option of the automatic trimap -> None (off: None or False) or the area cap handed to
+    vm_trimap_fill_enclosed: 0 (True: any area) or an integer >= 1."""
+    if fill is None or fill is False:
+        return None
+    if fill is True:
+        return 0
+    if isinstance(fill, (int, np.integer)) and not isinstance(fill, (bool, np.bool_)) and fill >= 1:
+        return int(fill)
+    raise ValueError("%s: fill is None / False (off), True (any area) or an integer area cap >= 1, got %r" % (who, fill))
+
+
+def trimap_fill_enclosed_workspace_bytes(n, h, w):
+    return lib().vm_trimap_fill_enclosed_workspace_bytes(n, h, w)
+
+
+def trimap_fill_enclosed(trimap, max_area=0, out=None, work=None):
+    """vm_trimap_fill_enclosed: trimap uint8 [n,h,w] -> uint8 [n,h,w] with 128 on every 4-connected component of zero
+    bytes that does not touch the frame's border and has at most ``max_area`` pixels (0: any area); every other byte is
+    copied (include/vmatting.h).  ``out``: a contiguous uint8 [n,h,w] device tensor, allocated when None; ``trimap``
+    itself fills in place.  ``work``: a uint8 device buffer of trimap_fill_enclosed_workspace_bytes(n, h, w), allocated
+    when None."""
+    who = "trimap_fill_enclosed"
+    n, h, w = _check_u8_stack(who, "trimap", trimap)
+    if isinstance(max_area, bool) or not isinstance(max_area, (int, np.integer)):
+        raise TypeError("%s: max_area must be an integer, got %r" % (who, max_area))
+    if max_area < 0:
+        raise ValueError("%s: max_area must be 0 (any area) or a cap >= 1, got %d" % (who, max_area))
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, h, w)):
+        raise ValueError("%s: out must be [n,h,w] = %s, got %s" % (who, (n, h, w), tuple(getattr(out, "shape", ()))))
+    out = _flow_buffer(who, "out", out, n * h * w, torch.uint8, trimap.device)
+    work = _flow_buffer(who, "work", work, trimap_fill_enclosed_workspace_bytes(n, h, w), torch.uint8, trimap.device)
+    check(lib().vm_trimap_fill_enclosed(_ptr(trimap), n, h, w, int(max_area), _ptr(out), _ptr(work), stream_handle()),
+          who)
+    return out.view(n, h, w)
+
+
 # ---------------------------------------------------------------- the background plate from the clip itself
 
 PLATE_MAX_SAMPLES = 64

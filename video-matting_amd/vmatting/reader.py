@@ -121,15 +121,46 @@ def score_matte(pred, gt, trimap=None):
     return {k: float(res[k][0]) for k in ("count", "sad", "mse", "grad")}
 
 
-def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None):
+def fill_enclosed(trimap_u8, max_area=0):
+    """A trimap with its enclosed background turned unknown: 128 on every 4-connected region of zero bytes that does not
+    touch the frame's border and has at most ``max_area`` pixels (0: any area), every other byte as it was
+    (ops.trimap_fill_enclosed, include/vmatting.h).  A region of sure background that the subject surrounds is far more
+    often foreground that matches the plate than background; a hole that reaches the border is not filled.  trimap_u8
+    uint8, one frame [H,W] or a stack [N,H,W]; numpy arrays return numpy, device tensors stay on the device."""
+    from vmatting import ops
+    who = "fill_enclosed"
+    device = isinstance(trimap_u8, torch.Tensor)
+    if not device:
+        trimap_u8 = np.ascontiguousarray(trimap_u8)
+    if trimap_u8.dtype not in (torch.uint8, np.dtype(np.uint8)):
+        raise TypeError("%s: the trimap must be uint8, got %s" % (who, trimap_u8.dtype))
+    if len(trimap_u8.shape) not in (2, 3) or min(trimap_u8.shape) < 1:
+        raise ValueError("%s: the trimap must be [H,W] or [N,H,W], got %s" % (who, tuple(trimap_u8.shape)))
+    if isinstance(max_area, bool) or not isinstance(max_area, (int, np.integer)):
+        raise TypeError("%s: max_area must be an integer, got %r" % (who, max_area))
+    if max_area < 0:
+        raise ValueError("%s: max_area must be 0 (any area) or a cap >= 1, got %d" % (who, max_area))
+    single = len(trimap_u8.shape) == 2
+    tri = trimap_u8[None] if single else trimap_u8
+    if device:
+        out = ops.trimap_fill_enclosed(tri.contiguous(), int(max_area))
+    else:
+        out = ops.trimap_fill_enclosed(torch.from_numpy(tri).cuda(), int(max_area)).cpu().numpy()
+    return out[0] if single else out
+
+
+def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, fill=None):
     """The trimap of a frame from its difference to the background plate: what FrameStream(trimap="auto") feeds the
     model, and the trimap of a clip's first frame for ClipStream's alpha0.  cmp_u8 uint8 BGR, one frame [H,W,3] or a
     stack [N,H,W,3]; bg_u8 uint8 [H,W,3] (one plate) or, with a stack, [N,H,W,3] -> uint8 [H,W] or [N,H,W]: 0 where the
     frame equals the plate within ``lo`` levels over a (2 r_bg + 1)^2 window, 255 where it differs by ``hi`` or more
     over a (2 r_fg + 1)^2 window, 128 elsewhere (ops.trimap_from_plate, include/vmatting.h; None: ops.PLATE_DEFAULTS,
-    which are untuned).  No shadow or exposure model.  numpy arrays return numpy, device tensors stay on the device."""
+    which are untuned).  No shadow or exposure model.  ``fill`` (FrameStream's ``auto_fill``): True, or an integer area
+    cap, turns the enclosed background of the result unknown (fill_enclosed); None or False leaves it.  numpy arrays
+    return numpy, device tensors stay on the device."""
     from vmatting import ops
     who = "trimap_from_plate"
+    cap = ops.check_fill(who, fill)
     if isinstance(cmp_u8, torch.Tensor) != isinstance(bg_u8, torch.Tensor):
         raise TypeError("%s: cmp and bg are both numpy arrays or both torch tensors" % who)
     given = {"lo": lo, "hi": hi, "r_bg": r_bg, "r_fg": r_fg}
@@ -146,7 +177,11 @@ def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None):
     if device:
         out = ops.trimap_from_plate(cmp.contiguous(), bg_u8.contiguous(), **opts)
     else:
-        out = ops.trimap_from_plate(torch.from_numpy(cmp).cuda(), torch.from_numpy(bg_u8).cuda(), **opts).cpu().numpy()
+        out = ops.trimap_from_plate(torch.from_numpy(cmp).cuda(), torch.from_numpy(bg_u8).cuda(), **opts)
+    if cap is not None:
+        ops.trimap_fill_enclosed(out, cap, out=out)
+    if not device:
+        out = out.cpu().numpy()
     return out[0] if single else out
 
 

@@ -19,7 +19,7 @@ the chunk's chain starts with the recurrence tri[j] = ops.trimap_propagate(tri[j
 the frames only, never on the model's output, so the forward stays chunked.
 
 ``trimap="auto"``: the user has no trimap at all.  The chunk's chain starts with ops.trimap_from_plate on the uploaded
-frames and the plate; nothing is kept between chunks.
+frames and the plate, followed with ``auto_fill`` by ops.trimap_fill_enclosed in place; nothing is kept between chunks.
 
 This is one process's share of a clip; sharding a clip across ranks stays video.shard's job.
 """
@@ -96,13 +96,17 @@ class FrameStream(SlotPipeline):
     ops.trimap_from_plate(cmp, bg, **auto_options) on the device: background where the frame equals the plate, foreground
     where it clearly differs, unknown in between (include/vmatting.h; no shadow or exposure model).  ``auto_options``: a
     dict over ops.PLATE_DEFAULTS (lo, hi, r_bg, r_fg).  The mattes are those of ``trimap=True`` fed with these trimaps,
-    bit for bit; reader.trimap_from_plate shows them.
+    bit for bit; reader.trimap_from_plate shows them.  ``auto_fill``: True, or an integer area cap, turns every region
+    of sure background that does not reach the frame's border (with a cap: and has at most that many pixels) unknown
+    (ops.trimap_fill_enclosed): foreground that matches the plate over a wide area is otherwise a hole in the subject
+    that no model output repairs.  A hole that reaches the border is not filled, and a real gap the subject encloses
+    becomes unknown too.  None (the default) or False: no fill.
 
     If the source raises, or yields a wrong shape, dtype or k, the chunks already taken are finished and yielded, the
     streams are synchronised, and the exception then propagates; the object can run again."""
 
     def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True, new_bg=None,
-                 flow=None, flow_options=None, grow=1, auto_options=None):
+                 flow=None, flow_options=None, grow=1, auto_options=None, auto_fill=None):
         h, w, chunk, depth = int(h), int(w), int(chunk), int(depth)
         if h < 1 or w < 1 or chunk < 1 or depth < 1:
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
@@ -125,6 +129,9 @@ class FrameStream(SlotPipeline):
                     raise ValueError("FrameStream: auto_options takes %s, got %r" % (sorted(opts), k))
                 opts[k] = v
             self.auto_options = dict(zip(("lo", "hi", "r_bg", "r_fg"), ops.check_plate_options("FrameStream", **opts)))
+        if auto_fill is not None and not self.auto:
+            raise ValueError("FrameStream: auto_fill goes with trimap=%r" % AUTO)
+        self.auto_fill = ops.check_fill("FrameStream: auto_fill", auto_fill)
         if not self.propagate and (flow is not None or flow_options is not None):
             raise ValueError("FrameStream: flow and flow_options go with trimap=%r" % PROPAGATE)
         self.grow = ops.check_grow("FrameStream", grow)
@@ -234,6 +241,9 @@ class FrameStream(SlotPipeline):
         if self.auto:  # one workspace for every slot: the chains run one after another on the compute stream
             self._auto_work = torch.zeros(ops.trimap_from_plate_workspace_bytes(self.chunk, self.h, self.w),
                                           dtype=torch.uint8, device=self.device)
+            if self.auto_fill is not None:
+                self._fill_work = torch.zeros(ops.trimap_fill_enclosed_workspace_bytes(self.chunk, self.h, self.w),
+                                              dtype=torch.uint8, device=self.device)
         self._slots = [_Slot(self) for _ in range(self.depth)]
         torch.cuda.synchronize(self.device)  # the plates and the zeroed pad channels, before another stream reads them
         if self.propagate and self.graph:
@@ -301,6 +311,8 @@ class FrameStream(SlotPipeline):
             self._trimaps(s, k, keyed)
         if self.auto:
             ops.trimap_from_plate(s.d_cmp[:k], bg, out=s.d_tri[:k], work=self._auto_work, **self.auto_options)
+            if self.auto_fill is not None:
+                ops.trimap_fill_enclosed(s.d_tri[:k], self.auto_fill, out=s.d_tri[:k], work=self._fill_work)
         ops.frames_from_u8(s.d_cmp[:k], bg, None if s.d_tri is None else s.d_tri[:k], out=s.frames[:k])
         self.model.forward(s.frames[:k], out=s.alpha[:k], overflow=s.flag)
         self._download(s, k)
@@ -317,6 +329,8 @@ class FrameStream(SlotPipeline):
                 self._trimaps(s, self.chunk, keyed)
             if self.auto:
                 ops.trimap_from_plate(s.d_cmp, bg, out=s.d_tri, work=self._auto_work, **self.auto_options)
+                if self.auto_fill is not None:
+                    ops.trimap_fill_enclosed(s.d_tri, self.auto_fill, out=s.d_tri, work=self._fill_work)
             ops.frames_from_u8(s.d_cmp, bg, s.d_tri, out=s.frames)
 
         graph = self.model.capture(s.frames, static=True, out=s.alpha, overflow=s.flag, pre=pre,
