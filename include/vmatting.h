@@ -97,6 +97,9 @@ const char* vm_last_error(void);
  *   "persist_all"    1 = every plain grid of >= persist_rounds rounds (A/B); "persist_rot" 0 = walkers rotate
  *                    through the output tiles for folded upconvs only (default), 1 = always, 2 = never
  *   "rows_kernel", "rows_min_blocks", "rows_min_cin", "rows_up"  row-stationary kernel dispatch (1, 400, 128, 0)
+ *   "rows_retire"    row-stationary kernel (bf16, 16-row tiles): 1 = a tile's output rows 0 and 1 are finished and
+ *                    stored inside its last step, beside the other wave's MFMAs (default), 0 = the whole epilogue
+ *                    after the step (bit-identical)
  *   "border_ks"      folded-upconv border pass granule split: 1 (default), 2 or 4
  *   "border_fuse"    the border pass in extra blocks of the folded kernel's own launch instead of a launch of its
  *                    own: 0 = off, 1 = in the streaming folded kernel, 2 = in the persistent one too (default;

@@ -687,6 +687,7 @@ static const OptDef conv_options[] = {
     {"rows_up", &g_opt.rows_up, OPT_ANY},
     {"rows_min_cin", &g_opt.rows_min_cin, OPT_ANY},
     {"rows_min_blocks", &g_opt.rows_min_blocks, OPT_ANY},
+    {"rows_retire", &g_opt.rows_retire, OPT_RANGE, 2, {0, 1}},
     {"thin_rounds", &g_opt.thin_rounds, OPT_RANGE, 2, {0, 64}},
     {"pack_frames", &g_opt.pack_frames, OPT_RANGE, 2, {0, 1}},
     {"up_skip", &g_opt.up_skip, OPT_RANGE, 2, {0, 1}},
@@ -704,6 +705,7 @@ static const OptDef conv_options[] = {
 #ifdef VM_STUDY
     {"patch_cfg", &g_opt.patch_cfg, OPT_RANGE, 2, {0, 31}},
     {"patch_ablate", &g_opt.patch_ablate, OPT_ANY},  // timing-only ablations: garbage results
+    {"rows_ablate", &g_opt.rows_ablate, OPT_RANGE, 2, {0, 2}},  // timing-only ablations of conv3x3_rows' epilogue
     {"softmax_abl", &g_opt.softmax_abl, OPT_ANY},    // timing-only ablations of the f32 refine kernel
     {"patch_rowslot", &g_opt.patch_rowslot, OPT_RANGE, 2, {0, 1}},
     {"pair_strip_abl", &g_opt.pair_strip_abl, OPT_ANY},  // timing-only ablations of the strip pair kernel

@@ -85,6 +85,9 @@ struct ConvArgs {
   // ring (output row 0 / 2H-1, column 0 / 2W-1) unwritten
   int bwant, bfuse, bblocks, bframes, bK_pad;
   const void* bw;
+  // row-stationary kernel: retire = 1 finishes output rows 0 and 1 of a tile inside its last granule's step
+  // (vm_set_option "rows_retire"); rabl (study build) = the tail epilogue's timing-only ablations
+  int retire, rabl;
 };
 
 // compile-time loop: f(std::integral_constant<int, I>) for I in [I, N)

@@ -28,6 +28,12 @@ struct ConvOptions {
   long rows_up = 0;            // 1: the folded upconvs too
   long rows_min_cin = 64;      // r04 A/B: conv2_1 (cin 64, 2040 blocks) +0.3 % on rows<16>; below 64 the
                                // 2-blocks-per-CU patch kernel hides prologue/epilogue better
+  // rows<16> bf16: 1 = at a tile's end output rows 0 and 1 (bias / act / pack, their pool) are finished and stored
+  // between the last step's two barriers, waves 0-3 before and waves 4-7 behind their MFMAs of input rows 4 and 5, and
+  // only rows 2 and 3 after the step; 0 = the whole epilogue after the step's last barrier (A/B, and the reference of
+  // tests/test_gpu_rows_retire.py).  Same-box A/B of the 1080p forward: +1.0 % (profiles/rows_retire_ab.txt)
+  long rows_retire = 1;
+  long rows_ablate = 0;  // (study build) rows<16> tail epilogue: 1 = skipped, 2 = arithmetic kept, nothing written
   long src_span_limit = 0x7ffffff0L;  // split-source byte span the 32-bit offset kernels take (option
                                       // "src_span_limit" lowers it for the fallback tests)
   long pair_strip = 1;  // vm_conv3x3_pair_first*: 1 = the strip-walking kernel (conv_pair.hip) where it applies

@@ -24,7 +24,9 @@
 // so each DMA has one granule to land and no wave waits on a fragment read right after a barrier.  The granule stream
 // runs on across the block's tiles (the next tile's first granules are in flight while the last ones of this tile
 // compute), and the epilogue works from registers (bias / affine / act, 8-byte stores, the 2x2 max-pool through a
-// lane exchange), so a tile change costs no LDS round trip, no block-wide barrier and no DMA latency.
+// lane exchange), so a tile change costs no LDS round trip, no block-wide barrier and no DMA latency.  The bf16
+// 16-row kernel finishes output rows 0 and 1 of a tile before B'(g+1) of its last granule, the two waves of a SIMD at
+// opposite ends of that interval (vm_set_option "rows_retire").
 #include <type_traits>
 
 #include "conv_dispatch.h"
@@ -313,6 +315,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void c
     // FC == 2: the two 16-channel fragments form one 32-channel group, and chunk_pair turns the lanes' 4-channel quads
     // into whole 16-byte chunks (chunk c16 of the group): one 16-byte store per pixel row instead of two 8-byte ones
     const int c16 = (ck & 1) ? 2 + (ck >> 1) : ck >> 1;
+#ifdef VM_STUDY
+    const bool wr = a.rabl != 2;  // timing-only ablation 2: every bf16 store lands out of range (nothing is written)
+#else
+    constexpr bool wr = true;
+#endif
 #pragma unroll
     for (int pf = 0; pf < 2; ++pf) {
       const int c = tt.c0 + pf * 16 + col;
@@ -363,7 +370,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void c
         } else if constexpr (FC == 2) {
           const int chan = cb + cg * C::CW + c16 * 8;
           const uint4 d = chunk_pair(pack4(v[o][0]), pack4(v[o][1]));
-          const bool ok = r < H && c < W && chan < ccap;
+          const bool ok = wr && r < H && c < W && chan < ccap;
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, d),
                                                  yrs, ok ? (pix * a.y_cstride + chan) * 2 : OOB, 0, 0);
         } else {
@@ -394,7 +401,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void c
               m[f][j] = fmaxf(t, u);
             }
           const int pr = r >> 1, pc = c >> 1;
-          const bool pok = (col & 1) == 0 && pr < PH && pc < PWo;
+          const bool pok = wr && (col & 1) == 0 && pr < PH && pc < PWo;
           if constexpr (SPL) {
             typedef __attribute__((ext_vector_type(4))) unsigned u4_t;
             typedef __attribute__((ext_vector_type(2))) unsigned u2_t;
@@ -444,6 +451,93 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void c
     }
   };
 
+  // The same epilogue by output-row pair, for the tile-end form of step() below (bf16, 16-row tiles, no folded upconv,
+  // no sigmoid: ConvArgs::retire).  Value for value the arithmetic of epilogue(): fma, relu, bf16x2_bits, chunk_pair,
+  // and for the pool the row pair's max, the DPP column exchange and the same masks, so every stored bit is the same.
+  constexpr bool RET = !SPL && TH == 16;
+  auto st16 = [](const __amdgpu_buffer_rsrc_t rs, const uint4 d, const int off) __attribute__((always_inline)) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, d), rs, off, 0, 0);
+  };
+  // output rows 2 op, 2 op + 1 of tile tt and their 2x2 pool, written out (the accumulators are left alone: restarting
+  // rows inside a branch made hipcc carry a second copy of all 64 accumulator registers through the step).  4
+  // stores, 6 with the pool (the counts step() adds to its wait).  The constants come from ctab with four 16-byte
+  // reads: cout is a multiple of 8, so a lane's 4 channels are all inside ccap or all past it, and those past it only
+  // feed chunks that are never stored.
+  auto retire_pair = [&](const RowTile& tt, const int op) __attribute__((always_inline)) {
+    // the lane's position, opaque to the optimiser: what derives from it is recomputed here (a handful of vector
+    // instructions) instead of being hoisted out of the step loop into registers the steps do not have
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const int ck = ln >> 4, col = ln & 15;
+    // (likewise the frame and view geometry: the products and sums of these that do not change from tile to tile
+    // would each take a scalar register through the whole loop, which has none to spare)
+    int H = a.H, W = a.W, ycs = a.y_cstride, yco = a.y_coff, ccap_ = ccap, act = a.act;
+    const int cout = a.cout;
+    asm volatile("" : "+s"(H), "+s"(W), "+s"(ycs), "+s"(yco), "+s"(ccap_), "+s"(act));
+    const int c16 = (ck & 1) ? 2 + (ck >> 1) : ck >> 1;
+    const bool relu = act == VM_ACT_RELU;
+    T* yb = uniform_ptr(reinterpret_cast<T*>(a.y) + yco + (long)tt.n * H * W * ycs);
+    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(yb, 0, 0x7ffffff0, 0x00020000);
+    float mul[FC][4], add[FC][4];
+#pragma unroll
+    for (int f = 0; f < FC; ++f) {
+      const float4* cp = reinterpret_cast<const float4*>(ctab + min(tt.n0 + cg * C::CW + f * 16 + 4 * ck, ccap_ - 4));
+      const float4 c0 = cp[0], c1 = cp[1];
+      mul[f][0] = c0.x, add[f][0] = c0.y, mul[f][1] = c0.z, add[f][1] = c0.w;
+      mul[f][2] = c1.x, add[f][2] = c1.y, mul[f][3] = c1.z, add[f][3] = c1.w;
+    }
+    const int chan = tt.n0 + cg * C::CW + c16 * 8;
+    const int r = tt.r0 + rg * R + 2 * op;  // even: the pool window's top row
+    float v[2][2][FC][4];                    // [row of the pair][pixel half][fragment][channel], after the activation
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int o = 2 * op + i;
+#pragma unroll
+      for (int pf = 0; pf < 2; ++pf) {
+        const int c = tt.c0 + pf * 16 + col;
+#pragma unroll
+        for (int f = 0; f < FC; ++f) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float t = fmaf(acc[o][f][pf][j], mul[f][j], add[f][j]);
+            v[i][pf][f][j] = relu ? fmaxf(t, 0.f) : t;
+          }
+        }
+        const uint2 lo = make_uint2(bf16x2_bits(v[i][pf][0][0], v[i][pf][0][1]), bf16x2_bits(v[i][pf][0][2], v[i][pf][0][3]));
+        const uint2 hi = make_uint2(bf16x2_bits(v[i][pf][FC - 1][0], v[i][pf][FC - 1][1]),
+                                    bf16x2_bits(v[i][pf][FC - 1][2], v[i][pf][FC - 1][3]));
+        st16(yrs, chunk_pair(lo, hi), r + i < H && c < W && chan < ccap_ ? (((r + i) * W + c) * ycs + chan) * 2 : OOB);
+      }
+    }
+    if (a.py) {
+      const int PH = (H + 1) >> 1, PWo = (W + 1) >> 1;
+      const int pcs = a.py_cstride, pco = a.py_coff;
+      T* pbp = uniform_ptr(reinterpret_cast<T*>(a.py) + pco + (long)tt.n * PH * PWo * pcs);
+      const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(pbp, 0, 0x7ffffff0, 0x00020000);
+#pragma unroll
+      for (int pf = 0; pf < 2; ++pf) {
+        const int c = tt.c0 + pf * 16 + col;
+        const bool v0 = r < H && c < W, v1 = r + 1 < H && c < W;
+        float m[FC][4];
+#pragma unroll
+        for (int f = 0; f < FC; ++f)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float t = v0 ? v[0][pf][f][j] : -INFINITY;
+            if (v1) t = fmaxf(t, v[1][pf][f][j]);
+            // column partner: lane col ^ 1 (DPP quad_perm [1,0,3,2])
+            const float u = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(t), 0xB1, 0xF, 0xF, false));
+            m[f][j] = fmaxf(t, u);
+          }
+        const int pr = r >> 1, pc = c >> 1;
+        const bool pok = (col & 1) == 0 && pr < PH && pc < PWo;
+        const uint2 lo = make_uint2(bf16x2_bits(m[0][0], m[0][1]), bf16x2_bits(m[0][2], m[0][3]));
+        const uint2 hi = make_uint2(bf16x2_bits(m[FC - 1][0], m[FC - 1][1]), bf16x2_bits(m[FC - 1][2], m[FC - 1][3]));
+        st16(prs, chunk_pair(lo, hi), pok && chan < cout ? ((pr * PWo + pc) * pcs + chan) * 2 : OOB);
+      }
+    }
+  };
+
   // the step stream: step s = granule g of local tile k; t0 / t1 / t2 = tiles k, k+1, k+2 (decoded once per tile)
   int s = 0, k = 0, g = 0;
   RowTile t0 = tile_of(0), t1 = tile_of(ntile > 1 ? 1 : 0), t2 = tile_of(ntile > 2 ? 2 : 0);
@@ -477,6 +571,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void c
   ldw(w1, 0, 1);
   ldw(w2, 0, 2);
 
+  // the tile-end form of a step (below): 0 = off, 1 = on and this wave is the first of its SIMD's two, 2 = the second
+  const int rmode = RET && a.retire ? (wave >= 4 ? 2 : 1) : 0;
   // one step; b = s & 1 is a compile-time constant (the loop runs step pairs), so every fragment address is a
   // per-lane base + an immediate offset.  sched_group_barrier pins the interleave: the fragment reads of input row
   // ir+2 (and of the next granule's weights) are spread over row ir's MFMAs, so LDS latency stays hidden.
@@ -504,6 +600,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void c
     __builtin_amdgcn_sched_barrier(0);
     sync(NX{});  // B(s+1): W(s+1) landed, X(s+1) may still fly
     __builtin_amdgcn_sched_barrier(0);
+    // Tile end under ConvArgs::retire: output rows 0 and 1 got their last products from input rows 2 and 3, so
+    // between B(s+1) and B'(s+1) they are finished (bias / affine / act, packed, pooled) and stored while the
+    // matrix pipe is busy: the two waves of a SIMD (w and w + 4) do it at opposite ends of the interval, waves 0-3
+    // here, before their MFMAs of input rows 4 and 5, waves 4-7 behind theirs, so each half's vector work runs
+    // beside the other half's 36 MFMAs instead of both halves' after the barrier with the pipe idle.
+    int rm = rmode;  // (opaque, so that its comparisons are made here and not kept as masks through the loop)
+    if constexpr (RET) asm volatile("" : "+s"(rm));
+    if constexpr (RET) {
+      if (rm == 1 && g == nch - 1) retire_pair(t0, 0);
+    }
     // W(s) lives in registers: its buffer takes W(s+2), pieces among rows 4, 5's MFMAs
     ldx(xb, b, 5);
     issue_step(2, true, b, I{}, std::integral_constant<int, 2>{});
@@ -516,9 +622,25 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void c
     row_mma(5, xb, k2);
     sched_tail<FC>();
     __builtin_amdgcn_sched_barrier(0);
-    sync(NW{});  // B'(s+1): X(s+1) landed, W(s+2) may still fly
+    // B'(s+1): X(s+1) landed, W(s+2) may still fly.  So may the 4 (6) stores of rows 0 and 1: like W(s+2) they were
+    // issued after X(s+1), in either order, so the count below is X(s+1)'s either way, and B(s+2) waits for W(s+2)
+    // and every store of the tile as it always did
+    if (rm && g == nch - 1) {
+      if (rm == 2) retire_pair(t0, 0);
+      if (a.py) sync(std::integral_constant<int, WPW + 6>{});
+      else sync(std::integral_constant<int, WPW + 4>{});
+    } else {
+      sync(NW{});
+    }
     if (g == nch - 1) {  // last granule of the tile: write it out, restart the accumulators
-      epilogue(t0);
+      if (rm) {
+        retire_pair(t0, 1);  // rows 2 and 3 had input rows 4 and 5 to wait for
+      } else {
+#ifdef VM_STUDY
+        if (a.rabl != 1)  // timing-only ablation 1: no epilogue at all
+#endif
+        epilogue(t0);
+      }
 #pragma unroll
       for (int o = 0; o < R; ++o)
 #pragma unroll
@@ -583,6 +705,15 @@ static int launch_th(ConvArgs& a, hipStream_t st) {
   if (sp * a.tiles_n > 0x7fffffffL) return fail(VM_EUNSUPPORTED, "conv3x3: too many tiles");
   a.tiles_total = (int)(sp * a.tiles_n);
   a.prio = (int)g_opt.conv_prio;
+  // the tile-end form of step(): the bf16 16-row kernel's plain convs (a folded upconv scatters its phases and a
+  // sigmoid is no work to set beside the partner wave's MFMAs: both keep the tail epilogue, like the f16x3 and 8-row
+  // forms)
+  a.retire = g_opt.rows_retire && TH == 16 && !SPL && !a.up && a.act != VM_ACT_SIGMOID;
+  a.rabl = 0;
+#ifdef VM_STUDY
+  a.rabl = (int)g_opt.rows_ablate;
+  if (a.rabl) a.retire = 0;  // the ablations time the tail epilogue
+#endif
   // persistent: one block per CU (LDS-limited), a multiple of 8 so every XCD gets the same number of blocks
   long grid = g_num_cu < a.tiles_total ? g_num_cu : a.tiles_total;
   grid = (grid + 7) / 8 * 8;
