@@ -877,6 +877,61 @@ int vm_matte_score(const void* pred, int pred_dtype, const void* gt, int gt_dtyp
                    const void* prev_pred, const void* prev_gt, const float* backward, int n, int h, int w,
                    double* stats, float* grad_map, void* work, void* stream);
 
+/* ---------------------------------------------------------------- guided matte upsampling
+ * A frame larger than the model should see (2160 x 3840) is reduced by s = 2, 3 or 4, the model runs on the reduced
+ * frame, and its matte is carried back up by a guided filter steered by the full-resolution frame (He & Sun, "Fast
+ * Guided Filter"; the reference has no counterpart, it runs at the frames' size).  With hm = ceil(h / s) and
+ * wm = ceil(w / s), three calls (csrc/guided.hip); tests/guided_ref.py restates each in numpy.
+ *
+ * frames_reduce_u8(src, s, kind) = dst, all integer:
+ *   src   uint8 [n,h,w,c] at any byte address; dst uint8 [n,hm,wm,c], not overlapping src
+ *   block output pixel (Y, X) stands for the input pixels y in [s Y, min(h, s Y + s)), x in [s X, min(w, s X + s)):
+ *         cnt of them, fewer in the ragged last row and column
+ *   VM_REDUCE_MEAN (c == 3)    per byte (2 sum + cnt) / (2 cnt) in integers: the block's mean, halves rounded up
+ *   VM_REDUCE_TRIMAP (c == 1)  the block's byte if all cnt bytes agree, else 128: a reduced 0 or 255 is still a hard
+ *                              claim about every pixel it stands for
+ * One thread makes 12 (mean) or 16 (trimap) output bytes; it reads every input row of its blocks as aligned dwords
+ * shifted into place, whatever the row's address, and stores dwords where the output row is 4-byte aligned.  Only the
+ * ragged last blocks of a row go byte by byte.
+ *
+ * guided_coeffs(g, p, r, eps) = ab: the linear model p ~ a . I + b around every low-resolution pixel
+ *   g     uint8 [n,hm,wm,3], the reduced frame; I = g / 255.  p f32 [n,hm,wm], the model's matte, 4-byte aligned
+ *   r     1..8: windows are (2 r + 1)^2, clipped to the image (N pixels; the image may be smaller than the window)
+ *   eps   1e-5 .. 1
+ *   Sigma = mean(I I^T) - mean(I) mean(I)^T + eps 1_3;  c = mean(I p) - mean(I) mean(p);  a = Sigma^-1 c;
+ *   b = mean(p) - a . mean(I);  (a, b) rounded to f32 once; ab = the mean of (a, b) over the same clipped window,
+ *   summed in f64, rounded to f32 once
+ *   ab    f32 [n,hm,wm,4] = (a_0, a_1, a_2, b), 16-byte aligned
+ *   work  vm_guided_workspace_bytes(n, hm, wm) bytes, 16-byte aligned: the unaveraged (a, b)
+ * The guide's moments (sums of bytes and of byte products) and N S_II - S_I S_I^T are exact integers; the moments with
+ * p and the 3 x 3 solve (L D L^T) are f64.  Sigma's conditioning is at most (0.75 + eps) / eps, which is what the
+ * lower bound on eps is for: the f64 error stays orders of magnitude below an f32 ulp, so ab differs from the f64
+ * restatement by the two f32 roundings only.  Two launches over 32 x 8 tiles staged in LDS with their r-pixel halo;
+ * each thread sums its window directly ((2 r + 1)^2 taps: the low-resolution side is a quarter of the pixels or less).
+ *
+ * guided_apply(ab, cmp, s) = alpha, f32 operation by operation, nothing contracted:
+ *   cmp   uint8 [n,h,w,3] at any byte address; alpha f32 [n,h,w], 4-byte aligned
+ *   fy = (f32(y) + 0.5f) / f32(s) - 0.5f clamped to [0, hm - 1]; y0 = floor(fy), y1 = min(y0 + 1, hm - 1), ty = fy - y0;
+ *   x likewise.  lerp(u, v, t) = u + t * (v - u).  Per component of (a, b):
+ *   m = lerp(lerp(ab[y0,x0], ab[y0,x1], tx), lerp(ab[y1,x0], ab[y1,x1], tx), ty): horizontally first
+ *   q = ((m_0 * I_0 + m_1 * I_1) + m_2 * I_2) + m_3, I_c = f32(cmp_c) / 255.0f;  alpha = min(max(q, 0), 1) (NaN -> 0)
+ * Traffic per pixel: 3 B read, 4 B written, and 16 / s^2 B of ab.  A lane owns 4 consecutive pixels of a column strip
+ * (the frame's 12 bytes as aligned dwords shifted into place, one 16-byte store where the row allows it) and walks 16
+ * rows; the fx weights are computed once per lane, the fy weights once per block, and a texel row is read and
+ * interpolated horizontally once per wave and strip, not per pixel.
+ * No allocation and no synchronisation inside any of the three: they can be captured in a graph.  VM_EINVAL for a NULL
+ * pointer, n, h or w < 1 (or 4 n h w beyond 2^31 - 1), s outside 2..4, an unknown kind or the wrong c for it, r or eps
+ * out of range (NaN included), a misaligned p / ab / work / alpha, or an output that overlaps an input (checked before
+ * any HIP call); the size query returns 0 for such shapes. */
+#define VM_REDUCE_MEAN 0
+#define VM_REDUCE_TRIMAP 1
+int vm_frames_reduce_u8(const uint8_t* src, int n, int h, int w, int c, int scale, int kind, uint8_t* dst,
+                        void* stream);
+size_t vm_guided_workspace_bytes(int n, int hm, int wm);
+int vm_guided_coeffs(const uint8_t* guide, const float* p, int n, int hm, int wm, int r, double eps, float* ab,
+                     void* work, void* stream);
+int vm_guided_apply(const float* ab, const uint8_t* cmp, int n, int h, int w, int scale, float* alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

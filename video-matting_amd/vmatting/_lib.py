@@ -22,6 +22,7 @@ ACT = {"none": 0, "relu": 1, "sigmoid": 2, "softmax": 3}
 VM_OK, VM_EINVAL, VM_EUNSUPPORTED, VM_EHIP, VM_EINDEX = 0, -1, -2, -3, -4
 ABI_VERSION = 1
 VM_COMPOSE_OVER, VM_COMPOSE_STRAIGHT, VM_COMPOSE_PREMUL = 0, 1, 2
+VM_REDUCE_MEAN, VM_REDUCE_TRIMAP = 0, 1
 
 c_void_p, c_int, c_float, c_long, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long, ctypes.c_size_t
 
@@ -213,6 +214,11 @@ SIGNATURES = [
     ("vm_matte_score_workspace_bytes", c_size_t, [c_int, c_int, c_int]),
     ("vm_matte_score", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vm_frames_reduce_u8", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("vm_guided_workspace_bytes", c_size_t, [c_int, c_int, c_int]),
+    ("vm_guided_coeffs", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p,
+                          c_void_p]),
+    ("vm_guided_apply", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 ]
 
 _lib = None

@@ -1454,6 +1454,163 @@ def score_summary(stats, first_has_prev=False, has_flow=False):
     return res
 
 
+# ---------------------------------------------------------------- guided matte upsampling
+
+SCALES = (2, 3, 4)
+REDUCE_KINDS = {"mean": (_lib.VM_REDUCE_MEAN, 3), "trimap": (_lib.VM_REDUCE_TRIMAP, 1)}  # kind -> (code, channels)
+# window radius on the reduced frame and the regulariser, the values of the CPU prototype; untuned on real footage
+# 
+GUIDED_DEFAULTS = {"r": 2, "eps": 1e-3}
+GUIDED_R_MAX, GUIDED_EPS_MIN, GUIDED_EPS_MAX = 8, 1e-5, 1.0
+
+
+def check_scale(who, scale, smallest=2):
+    """The reduction factor: an integer in ``smallest``..4 (an op takes 2..4; FrameStream also 1: no reduction)."""
+    if isinstance(scale, (bool, np.bool_)) or not isinstance(scale, (int, np.integer)):
+        raise TypeError("%s: scale must be an integer, got %r" % (who, scale))
+    if not smallest <= scale <= SCALES[-1]:
+        raise ValueError("%s: scale must be in %d..%d, got %d" % (who, smallest, SCALES[-1], scale))
+    return int(scale)
+
+
+def reduced_size(h, w, scale):
+    """(ceil(h / scale), ceil(w / scale)): the size the model runs at."""
+    return -(-int(h) // scale), -(-int(w) // scale)
+
+
+def check_guided_options(who, r=GUIDED_DEFAULTS["r"], eps=GUIDED_DEFAULTS["eps"]):
+    """The options of vm_guided_coeffs as it checks them, on the host: an integer r in 1..8 and a real eps in
+    [1e-5, 1] -> (r, eps)."""
+    if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, np.integer)):
+        raise TypeError("%s: r must be an integer, got %r" % (who, r))
+    if isinstance(eps, (bool, np.bool_)) or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise TypeError("%s: eps must be a real number, got %r" % (who, eps))
+    if not 1 <= r <= GUIDED_R_MAX:
+        raise ValueError("%s: r must be in 1..%d, got %d" % (who, GUIDED_R_MAX, r))
+    if not GUIDED_EPS_MIN <= eps <= GUIDED_EPS_MAX:  # (false for NaN)
+        raise ValueError("%s: eps must be in [%g, %g], got %r" % (who, GUIDED_EPS_MIN, GUIDED_EPS_MAX, eps))
+    return int(r), float(eps)
+
+
+def guided_options(who, options):
+    """A dict over GUIDED_DEFAULTS (None: the defaults), checked -> {"r": r, "eps": eps}."""
+    opts = dict(GUIDED_DEFAULTS)
+    for k, v in dict(options or {}).items():
+        if k not in opts:
+            raise ValueError("%s: guided options are %s, got %r" % (who, sorted(opts), k))
+        opts[k] = v
+    return dict(zip(("r", "eps"), check_guided_options(who, **opts)))
+
+
+def frames_reduce_u8(frames, scale, kind="mean", out=None):
+    """vm_frames_reduce_u8: uint8 frames to the model's resolution.  kind "mean": ``frames`` [n,h,w,3] -> [n,hm,wm,3],
+    per byte the mean of the scale x scale block, halves rounded up; kind "trimap": ``frames`` [n,h,w] -> [n,hm,wm],
+    the block's byte if all its pixels agree, else 128.  hm = ceil(h / scale), wm = ceil(w / scale); the last blocks of a
+    ragged frame are smaller (include/vmatting.h).  ``out``: a contiguous uint8 device tensor of the result's shape,
+    allocated when None."""
+    who = "frames_reduce_u8"
+    if kind not in REDUCE_KINDS:
+        raise ValueError("%s: kind must be one of %s, got %r" % (who, sorted(REDUCE_KINDS), kind))
+    code, c = REDUCE_KINDS[kind]
+    scale = check_scale(who, scale)
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError("%s: frames must be a torch tensor, got %s" % (who, type(frames).__name__))
+    if frames.dtype != torch.uint8:
+        raise TypeError("%s: frames must be uint8, got %s" % (who, frames.dtype))
+    want = "[n,h,w,3]" if c == 3 else "[n,h,w]"
+    if frames.dim() != (4 if c == 3 else 3) or min(frames.shape) < 1 or (c == 3 and frames.shape[3] != 3):
+        raise ValueError("%s: kind %r takes %s frames, got %s" % (who, kind, want, tuple(frames.shape)))
+    if not frames.is_contiguous():
+        raise ValueError("%s: frames must be contiguous" % who)
+    n, h, w = (int(v) for v in frames.shape[:3])
+    hm, wm = reduced_size(h, w, scale)
+    shape = (n, hm, wm) + ((3,) if c == 3 else ())
+    if out is not None:
+        _score_plane(who, "out", out, shape, (torch.uint8,))
+    _require_gpu(frames)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    _require_gpu(out)
+    check(lib().vm_frames_reduce_u8(_ptr(frames), n, h, w, c, scale, code, _ptr(out), stream_handle()), who)
+    return out
+
+
+def guided_workspace_bytes(n, hm, wm):
+    return lib().vm_guided_workspace_bytes(n, hm, wm)
+
+
+def guided_coeffs(guide_lo, alpha_lo, r=GUIDED_DEFAULTS["r"], eps=GUIDED_DEFAULTS["eps"], out=None, work=None):
+    """vm_guided_coeffs: the guided filter's linear model on the reduced frame.  ``guide_lo`` u8 [n,hm,wm,3], ``alpha_lo``
+    f32 [n,hm,wm] or [n,hm,wm,1] -> f32 [n,hm,wm,4] = (a_0, a_1, a_2, b): alpha_lo ~ a . guide_lo / 255 + b over the
+    clipped (2 r + 1)^2 window of every pixel, regularised by eps, then averaged over the same window
+    (include/vmatting.h).  ``out``: a contiguous f32 [n,hm,wm,4] device tensor; ``work``: a uint8 device buffer of
+    guided_workspace_bytes(n, hm, wm); both are allocated when None."""
+    who = "guided_coeffs"
+    if not isinstance(guide_lo, torch.Tensor):
+        raise TypeError("%s: guide_lo must be a torch tensor, got %s" % (who, type(guide_lo).__name__))
+    if guide_lo.dim() != 4 or guide_lo.shape[3] != 3 or min(guide_lo.shape) < 1:
+        raise ValueError("%s: guide_lo must be [n,hm,wm,3], got %s" % (who, tuple(guide_lo.shape)))
+    n, hm, wm = (int(v) for v in guide_lo.shape[:3])
+    _score_plane(who, "guide_lo", guide_lo, (n, hm, wm, 3), (torch.uint8,))
+    if not isinstance(alpha_lo, torch.Tensor):
+        raise TypeError("%s: alpha_lo must be a torch tensor, got %s" % (who, type(alpha_lo).__name__))
+    _score_plane(who, "alpha_lo", alpha_lo, (n, hm, wm, 1) if alpha_lo.dim() == 4 else (n, hm, wm), (torch.float32,))
+    r, eps = check_guided_options(who, r, eps)
+    if out is not None:
+        _score_plane(who, "out", out, (n, hm, wm, 4), (torch.float32,))
+    for t in (guide_lo, alpha_lo, out):
+        if t is not None:
+            _require_gpu(t)
+    if out is None:
+        out = torch.empty((n, hm, wm, 4), dtype=torch.float32, device=guide_lo.device)
+    work = _flow_buffer(who, "work", work, guided_workspace_bytes(n, hm, wm), torch.uint8, guide_lo.device)
+    check(lib().vm_guided_coeffs(_ptr(guide_lo), _ptr(alpha_lo), n, hm, wm, r, eps, _ptr(out), _ptr(work),
+                                 stream_handle()), who)
+    return out
+
+
+def guided_apply(ab, guide_hi, scale, out=None):
+    """vm_guided_apply: the matte at full resolution.  ``ab`` f32 [n,hm,wm,4] (guided_coeffs), ``guide_hi`` u8
+    [n,h,w,3] with hm = ceil(h / scale), wm = ceil(w / scale) -> f32 [n,h,w,1]: (a, b) interpolated bilinearly at the
+    pixel (half-pixel centres, clamped), alpha = min(max(a . guide_hi / 255 + b, 0), 1), in f32 operation by operation
+    (include/vmatting.h).  ``out``: a contiguous f32 [n,h,w,1] or [n,h,w] device tensor, allocated when None."""
+    who = "guided_apply"
+    scale = check_scale(who, scale)
+    if not isinstance(guide_hi, torch.Tensor):
+        raise TypeError("%s: guide_hi must be a torch tensor, got %s" % (who, type(guide_hi).__name__))
+    if guide_hi.dim() != 4 or guide_hi.shape[3] != 3 or min(guide_hi.shape) < 1:
+        raise ValueError("%s: guide_hi must be [n,h,w,3], got %s" % (who, tuple(guide_hi.shape)))
+    n, h, w = (int(v) for v in guide_hi.shape[:3])
+    _score_plane(who, "guide_hi", guide_hi, (n, h, w, 3), (torch.uint8,))
+    hm, wm = reduced_size(h, w, scale)
+    if not isinstance(ab, torch.Tensor):
+        raise TypeError("%s: ab must be a torch tensor, got %s" % (who, type(ab).__name__))
+    _score_plane(who, "ab", ab, (n, hm, wm, 4), (torch.float32,))
+    if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("%s: out must be a torch tensor, got %s" % (who, type(out).__name__))
+        _score_plane(who, "out", out, (n, h, w) if out.dim() == 3 else (n, h, w, 1), (torch.float32,))
+    for t in (ab, guide_hi, out):
+        if t is not None:
+            _require_gpu(t)
+    if out is None:
+        out = torch.empty((n, h, w, 1), dtype=torch.float32, device=guide_hi.device)
+    check(lib().vm_guided_apply(_ptr(ab), _ptr(guide_hi), n, h, w, scale, _ptr(out), stream_handle()), who)
+    return out
+
+
+def guided_upsample(alpha_lo, guide_hi, scale, r=GUIDED_DEFAULTS["r"], eps=GUIDED_DEFAULTS["eps"], guide_lo=None):
+    """The three in a row: ``alpha_lo`` f32 [n,hm,wm] or [n,hm,wm,1], the matte of the model on the frames reduced by
+    ``scale``, and the full-resolution frames ``guide_hi`` u8 [n,h,w,3] -> f32 [n,h,w,1].  ``guide_lo``: the reduced
+    frames the model saw (frames_reduce_u8(guide_hi, scale)); made here when None."""
+    who = "guided_upsample"
+    scale = check_scale(who, scale)
+    r, eps = check_guided_options(who, r, eps)
+    if guide_lo is None:
+        guide_lo = frames_reduce_u8(guide_hi, scale)
+    return guided_apply(guided_coeffs(guide_lo, alpha_lo, r, eps), guide_hi, scale)
+
+
 # ---------------------------------------------------------------- training step (train.py:288-343, config 5)
 
 def matting_loss_backward(pred, gt, raw_fg, in_bg, in_cmp, out=None):

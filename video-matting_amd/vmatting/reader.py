@@ -121,6 +121,33 @@ def score_matte(pred, gt, trimap=None):
     return {k: float(res[k][0]) for k in ("count", "sad", "mse", "grad")}
 
 
+def upsample_matte(alpha_lo, cmp_u8, scale, **options):
+    """The matte of a reduced frame carried back to the frame's size by a guided filter: what FrameStream(scale=...)
+    does with the model's output.  alpha_lo [hm,wm] f32 (or f64, rounded to f32 first), the matte of the model on
+    frames_reduce(cmp_u8, scale); cmp_u8 uint8 [h,w,3] BGR with hm = ceil(h / scale), wm = ceil(w / scale); ``scale``
+    2..4; ``options`` over ops.GUIDED_DEFAULTS (r, eps) -> f32 [h,w] in [0,1] (ops.guided_upsample, include/vmatting.h).
+    numpy in, numpy out, through the kernels."""
+    from vmatting import ops
+    who = "upsample_matte"
+    scale = ops.check_scale(who, scale)
+    opts = ops.guided_options(who, options)
+    alpha_lo, cmp_u8 = np.asarray(alpha_lo), np.asarray(cmp_u8)
+    if alpha_lo.dtype == np.float64:
+        alpha_lo = alpha_lo.astype(np.float32)
+    if alpha_lo.dtype != np.float32:
+        raise TypeError("%s: alpha_lo must be float32 or float64, got %s" % (who, alpha_lo.dtype))
+    if cmp_u8.dtype != np.uint8:
+        raise TypeError("%s: cmp must be uint8, got %s" % (who, cmp_u8.dtype))
+    if cmp_u8.ndim != 3 or cmp_u8.shape[2] != 3 or cmp_u8.size == 0:
+        raise ValueError("%s: cmp must be [h,w,3] BGR, got %s" % (who, cmp_u8.shape))
+    lo = ops.reduced_size(cmp_u8.shape[0], cmp_u8.shape[1], scale)
+    if alpha_lo.shape != lo:
+        raise ValueError("%s: alpha_lo must be [hm,wm] = %s for cmp %s at scale %d, got %s" %
+                         (who, lo, cmp_u8.shape, scale, alpha_lo.shape))
+    dev = [torch.from_numpy(np.ascontiguousarray(a)[None]).cuda() for a in (alpha_lo, cmp_u8)]
+    return ops.guided_upsample(dev[0], dev[1], scale, **opts)[0, :, :, 0].cpu().numpy()
+
+
 def fill_enclosed(trimap_u8, max_area=0):
     """A trimap with its enclosed background turned unknown: 128 on every 4-connected region of zero bytes that does not
     touch the frame's border and has at most ``max_area`` pixels (0: any area), every other byte as it was

@@ -21,6 +21,11 @@ the frames only, never on the model's output, so the forward stays chunked.
 ``trimap="auto"``: the user has no trimap at all.  The chunk's chain starts with ops.trimap_from_plate on the uploaded
 frames and the plate, followed with ``auto_fill`` by ops.trimap_fill_enclosed in place; nothing is kept between chunks.
 
+``scale=2..4``: the frames are larger than the model should see (2160 x 3840).  The chunk's chain reduces the uploaded
+frames (and per-frame backgrounds and trimaps) by ``scale`` (ops.frames_reduce_u8), runs the model on the reduced
+frames, and carries its matte back to the frames' size with a guided filter steered by the full-resolution frame
+(ops.guided_coeffs, ops.guided_apply); the download then works on full-resolution data as ever.
+
 This is one process's share of a clip; sharding a clip across ranks stays video.shard's job.
 """
 
@@ -57,8 +62,17 @@ class _Slot(Slot):
             if fs.estimate:
                 self.d_bw = torch.zeros((n, h, w, 2), dtype=torch.float32, device=fs.device)
         self.graphs = {}  # trimap="propagate": the full-chunk graph of a keyed item (True) and of a continued one
+        if fs.scale > 1:
+            # the model's side of the chunk: the reduced uint8 frames it is fed from, its matte, and the guided
+            # filter's coefficients; the frame buffer below is then the model's size too
+            h, w = fs.hm, fs.wm
+            self.r_cmp = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device)
+            self.r_bg = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device) if fs.static_bg is None else None
+            self.r_tri = torch.zeros((n, h, w), dtype=u8, device=fs.device) if fs.trimap else None
+            self.alpha_lo = torch.empty((n, h, w, 1), dtype=torch.float32, device=fs.device)
+            self.ab = torch.empty((n, h, w, 4), dtype=torch.float32, device=fs.device)
         self.frames = ops.frame_buffer(fs.model, n, h, w)
-        self.alpha = torch.empty((n, h, w, 1), dtype=torch.float32, device=fs.device)
+        self.alpha = torch.empty((n, fs.h, fs.w, 1), dtype=torch.float32, device=fs.device)
         self.graph = None
         self.k = 0       # frames of the chunk in flight
 
@@ -102,16 +116,33 @@ class FrameStream(SlotPipeline):
     that no model output repairs.  A hole that reaches the border is not filled, and a real gap the subject encloses
     becomes unknown too.  None (the default) or False: no fill.
 
+    ``scale`` (1..4, default 1: off): run the model on frames reduced by ``scale`` and upsample its matte with a guided
+    filter.  ``h, w`` stay the frames' size, and so do all source items and results; the model runs at
+    ceil(h / scale) x ceil(w / scale).  cmp and per-frame backgrounds (the static plate once) are reduced to block means,
+    trimaps - given, propagated or automatic, all made at full resolution first - to the block's label where all its
+    pixels agree and unknown elsewhere (ops.frames_reduce_u8).  The full-resolution matte is
+    ops.guided_upsample(model matte, cmp, scale, **guided_options): per reduced pixel a linear model of the matte in the
+    frame's colours over a (2 r + 1)^2 window, regularised by eps, interpolated to every full-resolution pixel and applied
+    to its colour (He & Sun, "Fast Guided Filter"; include/vmatting.h).  ``guided_options``: a dict over
+    ops.GUIDED_DEFAULTS (r, eps; untuned on real footage), only with scale > 1.  Every ``out`` mode works on the
+    full-resolution matte.  scale=1 is the stream without any of this, call for call.
+
     If the source raises, or yields a wrong shape, dtype or k, the chunks already taken are finished and yielded, the
     streams are synchronised, and the exception then propagates; the object can run again."""
 
     def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True, new_bg=None,
-                 flow=None, flow_options=None, grow=1, auto_options=None, auto_fill=None):
+                 flow=None, flow_options=None, grow=1, auto_options=None, auto_fill=None, scale=1, guided_options=None):
         h, w, chunk, depth = int(h), int(w), int(chunk), int(depth)
         if h < 1 or w < 1 or chunk < 1 or depth < 1:
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
                              (h, w, chunk, depth))
         check_out("FrameStream", out)
+        self.scale = ops.check_scale("FrameStream", scale, smallest=1)
+        if guided_options is not None and self.scale == 1:
+            raise ValueError("FrameStream: guided_options go with scale > 1")
+        if self.scale > 1:
+            self.guided = ops.guided_options("FrameStream", guided_options)
+            self.hm, self.wm = ops.reduced_size(h, w, self.scale)
         if isinstance(trimap, str) and trimap not in (PROPAGATE, AUTO):
             raise ValueError("FrameStream: trimap must be True, False, %r or %r, got %r" % (PROPAGATE, AUTO, trimap))
         self.propagate = isinstance(trimap, str) and trimap == PROPAGATE
@@ -156,6 +187,7 @@ class FrameStream(SlotPipeline):
         self.device = model.device
         self.overflowed_chunks = []
         self._plate = self._new_plate = None
+        self._plate_lo = self._guided_work = None  # scale > 1: the reduced plate, the guided filter's workspace
         self._x6 = None
         self._keyed = False      # trimap="propagate": whether this run has had its first key
         self._tri_last = None    # ... and the last frame's trimap, at a fixed device address
@@ -234,6 +266,11 @@ class FrameStream(SlotPipeline):
         self._make_streams()
         if self.static_bg is not None:
             self._plate = torch.from_numpy(self.static_bg).to(self.device)
+        if self.scale > 1:  # the plate at the model's size, once; one workspace for every slot, like _auto_work
+            if self._plate is not None:
+                self._plate_lo = ops.frames_reduce_u8(self._plate[None], self.scale)
+            self._guided_work = torch.zeros(ops.guided_workspace_bytes(self.chunk, self.hm, self.wm), dtype=torch.uint8,
+                                            device=self.device)
         if isinstance(self.new_bg, np.ndarray):
             self._new_plate = torch.from_numpy(self.new_bg).to(self.device)
         if self.propagate:
@@ -297,6 +334,32 @@ class FrameStream(SlotPipeline):
             raise RuntimeError("FrameStream: last_trimap() before any frame was submitted")
         return self._tri_last.cpu().numpy()
 
+    def _feed(self, s, k, bg):
+        """The network input of the slot's first k frames from its uint8 frames; with scale > 1 from their reductions."""
+        tri = None if s.d_tri is None else s.d_tri[:k]
+        if self.scale == 1:
+            ops.frames_from_u8(s.d_cmp[:k], bg, tri, out=s.frames[:k])
+            return
+        ops.frames_reduce_u8(s.d_cmp[:k], self.scale, out=s.r_cmp[:k])
+        if self._plate is None:
+            bg = ops.frames_reduce_u8(bg, self.scale, out=s.r_bg[:k])
+        else:
+            bg = self._plate_lo
+        if tri is not None:
+            tri = ops.frames_reduce_u8(tri, self.scale, "trimap", out=s.r_tri[:k])
+        ops.frames_from_u8(s.r_cmp[:k], bg, tri, out=s.frames[:k])
+
+    def _matte(self, s, k):
+        """Where the model's matte of the slot's first k frames goes: the slot's alpha, or with scale > 1 its reduced
+        twin."""
+        return s.alpha[:k] if self.scale == 1 else s.alpha_lo[:k]
+
+    def _upsample(self, s, k):
+        """scale > 1: the model's reduced matte to the slot's full-resolution alpha, steered by the uploaded frames."""
+        if self.scale > 1:
+            ops.guided_coeffs(s.r_cmp[:k], s.alpha_lo[:k], out=s.ab[:k], work=self._guided_work, **self.guided)
+            ops.guided_apply(s.ab[:k], s.d_cmp[:k], self.scale, out=s.alpha[:k])
+
     def _download(self, s, k):
         """The result of the slot's first k frames from its alpha (and, composed, its uint8 inputs)."""
         bg = self._plate if self._plate is not None else s.d_bg[:k]
@@ -313,8 +376,9 @@ class FrameStream(SlotPipeline):
             ops.trimap_from_plate(s.d_cmp[:k], bg, out=s.d_tri[:k], work=self._auto_work, **self.auto_options)
             if self.auto_fill is not None:
                 ops.trimap_fill_enclosed(s.d_tri[:k], self.auto_fill, out=s.d_tri[:k], work=self._fill_work)
-        ops.frames_from_u8(s.d_cmp[:k], bg, None if s.d_tri is None else s.d_tri[:k], out=s.frames[:k])
-        self.model.forward(s.frames[:k], out=s.alpha[:k], overflow=s.flag)
+        self._feed(s, k, bg)
+        self.model.forward(s.frames[:k], out=self._matte(s, k), overflow=s.flag)
+        self._upsample(s, k)
         self._download(s, k)
 
     def _capture(self, s, keyed=None):
@@ -331,10 +395,14 @@ class FrameStream(SlotPipeline):
                 ops.trimap_from_plate(s.d_cmp, bg, out=s.d_tri, work=self._auto_work, **self.auto_options)
                 if self.auto_fill is not None:
                     ops.trimap_fill_enclosed(s.d_tri, self.auto_fill, out=s.d_tri, work=self._fill_work)
-            ops.frames_from_u8(s.d_cmp, bg, s.d_tri, out=s.frames)
+            self._feed(s, self.chunk, bg)
 
-        graph = self.model.capture(s.frames, static=True, out=s.alpha, overflow=s.flag, pre=pre,
-                                   post=lambda: self._download(s, self.chunk))
+        def post():
+            self._upsample(s, self.chunk)
+            self._download(s, self.chunk)
+
+        graph = self.model.capture(s.frames, static=True, out=self._matte(s, self.chunk), overflow=s.flag, pre=pre,
+                                   post=post)
         if keyed is None:
             s.graph = graph
         else:
@@ -368,8 +436,9 @@ class FrameStream(SlotPipeline):
             # the chunk left fp16's range: the same frames on bf16x6 (f32 range), re-quantised and re-downloaded
             self.overflowed_chunks.append(s.index)
             with torch.cuda.stream(self._compute):
-                rerun_x6(self, s.frames[:k], s.alpha[:k])
+                rerun_x6(self, s.frames[:k], self._matte(s, k))
                 s.flag.zero_()
+                self._upsample(s, k)
                 self._download(s, k)
             self._compute.synchronize()
         return s.h_out[:k].numpy().copy()

@@ -322,8 +322,11 @@ class UNet:
         ops.conv3x3(b["cat2"], C["conv2_3"], "relu", out=b["c23"])
         alpha = b["out"] if out is None else out
         # lean: upconv_4 takes conv1_5's shares of its own half of cat1 in its epilogue too, so neither half of cat1
-        # reaches HBM and the head only sums the two partial sets (.upconv4 is evaluated on first access)
-        self._up_valid = not (lean and self.fuse_up_head and "upconv_4" in self.fold_upconv and ops.upconv3x3_head(
+        # reaches HBM and the head only sums the two partial sets (.upconv4 is evaluated on first access).  Only where
+        # level 0 is exactly twice level 1: an odd frame height or width takes the resize path below
+        split_up = lean and self.fuse_up_head and "upconv_4" in self.fold_upconv
+        split_up = split_up and (h, w) == (2 * b["c23"].shape[1], 2 * b["c23"].shape[2])
+        self._up_valid = not (split_up and ops.upconv3x3_head(
             b["c23"], C["upconv_4"], self._head_up[0], 0, b["upart"], "none", out=b["cat1"][..., :64],
             store_y=False) is not None)
         if self._up_valid:
