@@ -276,13 +276,6 @@ fill_emit_kernel(const uint8_t* trimap, int n, int h, int w, int segs, unsigned 
   }
 }
 
-inline bool shape_ok(int n, int h, int w) { return n >= 1 && h >= 1 && w >= 1 && (long)n * h * w <= (long)INT_MAX; }
-
-inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + nb && pb < pa + na;
-}
-
 // the tile, seam and finish launches: the final labels of every frame in `labels`
 template <int MODE>
 void label_launches(const uint8_t* mask, int n, int h, int w, int value, bool eight, int* labels, int* aux,

@@ -359,10 +359,6 @@ apply_kernel(const float4* __restrict__ ab, const uint8_t* __restrict__ cmp, flo
   }
 }
 
-inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + nb && pb < pa + na;
-}
 inline bool shape_ok(int n, int h, int w, int c) {
   return n >= 1 && h >= 1 && w >= 1 && (long)n * h * w * c <= 2147483647l;
 }

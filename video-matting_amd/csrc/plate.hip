@@ -204,11 +204,6 @@ constexpr std::array<PlateKernel, sizeof...(I)> kernels_by_n(std::index_sequence
   return {{plate_kernel<(int)I + 1>...}};
 }
 
-inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace
 }  // namespace vm
 

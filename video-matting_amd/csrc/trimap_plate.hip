@@ -222,15 +222,6 @@ plate_erode_emit_kernel(const unsigned long long* __restrict__ work, int h, int 
   }
 }
 
-inline int row_words(int w) { return (w + 63) / 64; }
-
-inline bool shape_ok(int n, int h, int w) { return n >= 1 && h >= 1 && w >= 1 && (long)n * h * w <= (long)INT_MAX; }
-
-inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace
 }  // namespace vm
 

@@ -158,8 +158,6 @@ trimap_gather_kernel(const void* __restrict__ src, const float2* __restrict__ fl
   }
 }
 
-inline int map_words(int w) { return (w + 63) / 64; }
-
 }  // namespace
 }  // namespace vm
 
@@ -167,7 +165,7 @@ using namespace vm;
 
 extern "C" size_t vm_trimap_propagate_workspace_bytes(int h, int w, int grow) {
   if (h < 1 || w < 1 || grow < 1 || grow > GROW_MAX || (long)h * w > PIXELS_MAX) return 0;
-  return (size_t)h * map_words(w) * 16;
+  return (size_t)h * row_words(w) * 16;
 }
 
 extern "C" int vm_trimap_propagate(const uint8_t* prev, const float* flow, int h, int w, int grow, uint8_t* out,
@@ -182,7 +180,7 @@ extern "C" int vm_trimap_propagate(const uint8_t* prev, const float* flow, int h
   if (grow > 0 && reinterpret_cast<uintptr_t>(work) % 16)
     return fail(VM_EINVAL, "trimap_propagate: the workspace must be 16-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int words = map_words(w);
+  const int words = row_words(w);
   const bool vec = reinterpret_cast<uintptr_t>(out) % 16 == 0;
   const dim3 grid(((long)h * w + GATHER_BLOCK - 1) / GATHER_BLOCK);
   const float2* fl = reinterpret_cast<const float2*>(flow);

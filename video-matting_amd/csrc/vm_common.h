@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 
@@ -224,5 +225,16 @@ inline int grid_for(long work, int block, int max_blocks = 256 * 16) {
   if (g < 1) g = 1;
   return static_cast<int>(g);
 }
+
+// host-side argument checks shared by the frame ops' entry points
+inline bool shape_ok(int n, int h, int w) { return n >= 1 && h >= 1 && w >= 1 && (long)n * h * w <= (long)INT_MAX; }
+
+inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+
+// 64-bit words of one row of a bit-plane map
+inline int row_words(int w) { return (w + 63) / 64; }
 
 }  // namespace vm

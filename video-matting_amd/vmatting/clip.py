@@ -29,7 +29,6 @@ from .pipeline import PER_FRAME, Slot, SlotPipeline, check_new_bg, check_out, ch
 from .unet_simple import UNetSimple
 
 PROMOTE = ("numpy1", "numpy2")
-FLOW_MODES = ("given", "estimate")
 
 
 class _Slot(Slot):
@@ -99,19 +98,13 @@ class ClipStream(SlotPipeline):
         thresh = float(thresh)
         if not thresh >= 0.0:
             raise ValueError("ClipStream: thresh must be a non-negative number, got %r" % (thresh,))
-        if flow not in FLOW_MODES:
-            raise ValueError("ClipStream: flow must be one of %s, got %r" % (FLOW_MODES, flow))
+        if flow not in ops.FLOW_MODES:
+            raise ValueError("ClipStream: flow must be one of %s, got %r" % (ops.FLOW_MODES, flow))
         self.estimate = flow == "estimate"
         if flow_options is not None and not self.estimate:
             raise ValueError("ClipStream: flow_options go with flow='estimate'")
-        opts = dict(ops.FLOW_DEFAULTS)
-        for k, v in dict(flow_options or {}).items():
-            if k not in opts:
-                raise ValueError("ClipStream: flow_options takes %s, got %r" % (sorted(opts), k))
-            opts[k] = v
         if self.estimate:
-            self.flow_options = dict(zip(("levels", "warps", "iters", "alpha"),
-                                         ops.check_flow_options("ClipStream", h, w, **opts)))
+            self.flow_options = ops.flow_options("ClipStream: flow_options", h, w, flow_options)
         static_bg = check_static_bg("ClipStream", static_bg, h, w)
         self.new_bg = check_new_bg("ClipStream", out, new_bg, h, w)
         self.model, self.h, self.w, self.depth = model, h, w, depth

@@ -8,6 +8,7 @@ tf.concat is expressed without copies.
 """
 
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -858,6 +859,87 @@ def trimap_from_matte(matte, dilate=1, crop=3, out=None):
     return out
 
 
+# ---------------------------------------------------------------- argument checks of the frame ops (host only)
+
+def check_int(who, name, v, lo=None, hi=None):
+    """``v``, a Python or numpy integer (no bool) within lo..hi, both ends included (None: open) -> int."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise TypeError("%s: %s must be an integer, got %r" % (who, name, v))
+    if (lo is not None and v < lo) or (hi is not None and v > hi):
+        want = "at least %d" % lo if hi is None else "at most %d" % hi if lo is None else "in %d..%d" % (lo, hi)
+        raise ValueError("%s: %s must be %s, got %d" % (who, name, want, v))
+    return int(v)
+
+
+@functools.lru_cache(maxsize=None)
+def _parse_shapes(shapes):
+    """"n,h,w | n,h,w,1" -> (("n", "h", "w"), ("n", "h", "w", 1))."""
+    return tuple(tuple(int(d) if d.isdigit() else d for d in s.strip().split(",")) for s in shapes.split("|"))
+
+
+def _check_tensor(who, name, t, dtypes, shapes, wrong=TypeError, **dims):
+    """``t`` is a contiguous torch tensor of one of ``dtypes`` whose shape is one of ``shapes`` -> that shape, as ints.
+    ``shapes``: alternatives like "n,h,w | n,h,w,1"; a number stands for itself, a letter for the size ``dims`` gives it
+    or, where it gives none, for any size >= 1.  ``wrong``: what a non-tensor or another dtype raises; a shape or strides
+    raise ValueError.  The device is never looked at: _require_gpu is every op's last check."""
+    if not isinstance(t, torch.Tensor):
+        raise wrong("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
+    if t.dtype not in dtypes:
+        raise wrong("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
+    shape = tuple(int(v) for v in t.shape)
+    for spec in _parse_shapes(shapes):
+        if len(spec) == len(shape) and all(v == dims[d] if d in dims else v >= 1 if isinstance(d, str) else v == d
+                                           for v, d in zip(shape, spec)):
+            break
+    else:
+        sizes = ", ".join("%s=%d" % kv for kv in dims.items())
+        raise ValueError("%s: %s must be %s%s, got %s" % (who, name, " or ".join("[%s]" % s.strip() for s in
+                                                                                 shapes.split("|")),
+                                                          " with " + sizes if sizes else "", shape))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+    return shape
+
+
+def _out_or_new(who, name, t, dtype, shapes, device, wrong=TypeError, **dims):
+    """A caller's result tensor, checked as _check_tensor does, or a new one of the first of ``shapes`` (whose letters
+    ``dims`` all gives) on ``device``."""
+    if t is None:
+        return torch.empty(tuple(dims.get(d, d) for d in _parse_shapes(shapes)[0]), dtype=dtype, device=device)
+    _check_tensor(who, name, t, (dtype,), shapes, wrong, **dims)
+    return t
+
+
+def _buffer_or_new(who, name, t, dtype, numel, device):
+    """A caller's contiguous device buffer of at least ``numel`` elements (a workspace, a pyramid), or a new one.  Its
+    size is the library's to tell, so this comes after the inputs' _require_gpu."""
+    if t is None:
+        return torch.empty(numel, dtype=dtype, device=device)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() < numel or not t.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous %s tensor of at least %d elements" % (who, name, dtype, numel))
+    _require_gpu(t)
+    return t
+
+
+def _check_frames_and_bg(who, cmp, bg):
+    """Decoded frames as contiguous torch tensors: cmp u8 [n,h,w,3], bg u8 [n,h,w,3] or one plate -> (n, h, w, nb)."""
+    n, h, w, _ = _check_tensor(who, "cmp", cmp, (torch.uint8,), "n,h,w,3")
+    shape = _check_tensor(who, "bg", bg, (torch.uint8,), "n,h,w,3 | 1,h,w,3 | h,w,3", n=n, h=h, w=w)
+    return n, h, w, (n if shape == (n, h, w, 3) else 1)
+
+
+def _options(who, defaults, options, check, *args):
+    """A family's options: ``options`` (a dict, or None) over ``defaults``, through the family's
+    ``check(who, *args, **options)`` (-> the checked values in the defaults' key order) -> a dict in that order.  An
+    unknown key is a ValueError."""
+    opts = dict(defaults)
+    for k, v in dict(options or {}).items():
+        if k not in opts:
+            raise ValueError("%s takes %s, got %r" % (who, sorted(opts), k))
+        opts[k] = v
+    return dict(zip(defaults, check(who, *args, **opts)))
+
+
 # ---------------------------------------------------------------- inference on a decoded clip
 
 def _check_u8_frames(cmp, bg, trimap):
@@ -893,21 +975,20 @@ def frames_from_u8(cmp, bg, trimap=None, out=None, dtype=torch.float32):
     trimap, 6 without): channels = f32((double)u - VGG_MEAN) and f32((double)u / 255 - .5) as the reference feeds them.
     ``out``: an f32 NHWC view (dense or a channel slice), or the [..., :C] view of a bf16 [n,h,w,8] buffer (whose
     channels C..7 are zeroed); allocated in ``dtype`` when None."""
-    n, h, w, nb = _check_u8_frames(cmp, bg, trimap)
-    for t in (cmp, bg) + (() if trimap is None else (trimap,)):
-        _require_gpu(t)
-        if not t.is_contiguous():
-            raise ValueError("frames_from_u8: contiguous uint8 tensors expected")
+    who = "frames_from_u8"
+    n, h, w, nb = _check_frames_and_bg(who, cmp, bg)
+    if trimap is not None:
+        _check_tensor(who, "trimap", trimap, (torch.uint8,), "n,h,w", n=n, h=h, w=w)
     c = 6 if trimap is None else 7
-    if out is None:
-        if dtype == torch.bfloat16:
-            out = torch.empty((n, h, w, 8), dtype=torch.bfloat16, device=cmp.device)[..., :c]
-        elif dtype == torch.float32:
-            out = torch.empty((n, h, w, c), dtype=torch.float32, device=cmp.device)
-        else:
-            raise TypeError("frames_from_u8: f32 or bf16 output, got %s" % dtype)
-    if tuple(out.shape) != (n, h, w, c):
+    if out is None and dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("frames_from_u8: f32 or bf16 output, got %s" % dtype)
+    if out is not None and tuple(out.shape) != (n, h, w, c):
         raise ValueError("frames_from_u8: out must be [n,h,w,%d] = %s, got %s" % (c, (n, h, w, c), tuple(out.shape)))
+    for t in (cmp, bg, trimap):
+        if t is not None:
+            _require_gpu(t)
+    if out is None:
+        out = torch.empty((n, h, w, 8 if dtype == torch.bfloat16 else c), dtype=dtype, device=cmp.device)[..., :c]
     ov = nhwc(out)
     check(lib().vm_frames_from_u8(_ptr(cmp), _ptr(bg), _ptr(trimap), nb, ctypes.byref(ov), stream_handle()),
           "frames_from_u8")
@@ -917,12 +998,12 @@ def frames_from_u8(cmp, bg, trimap=None, out=None, dtype=torch.float32):
 def matte_quantize(alpha, out=None, bits=8):
     """vm_matte_quantize: f32 alpha (any shape, contiguous) -> uint8 (bits 8) or uint16 (bits 16) of the same shape:
     min(max(rint(alpha * M), 0), M), M = 255 / 65535, ties to even, NaN -> 0."""
-    _require_gpu(alpha)
     if bits not in (8, 16):
         raise ValueError("matte_quantize: bits 8 or 16, got %r" % (bits,))
     qt = torch.uint8 if bits == 8 else torch.uint16
-    if alpha.dtype != torch.float32 or not alpha.is_contiguous():
+    if isinstance(alpha, torch.Tensor) and (alpha.dtype != torch.float32 or not alpha.is_contiguous()):
         raise ValueError("matte_quantize: contiguous f32 alpha expected")
+    _require_gpu(alpha)
     if out is None:
         out = torch.empty(alpha.shape, dtype=qt, device=alpha.device)
     _require_gpu(out)
@@ -949,32 +1030,17 @@ def matte_compose(alpha, cmp, bg, new_bg=None, mode="over", out=None):
         raise ValueError("matte_compose: mode 'over' needs new_bg")
     if not over and new_bg is not None:
         raise ValueError("matte_compose: mode %r takes no new_bg" % mode)
-    if not isinstance(alpha, torch.Tensor):
-        raise TypeError("matte_compose: alpha must be a torch tensor, got %s" % type(alpha).__name__)
-    if alpha.dtype != torch.float32:
-        raise TypeError("matte_compose: alpha must be float32, got %s" % alpha.dtype)
-    n, h, w, nb = _check_u8_frames(cmp, bg, None)
-    if tuple(alpha.shape) not in ((n, h, w), (n, h, w, 1)):
-        raise ValueError("matte_compose: alpha must be [n,h,w] or [n,h,w,1] for cmp %s, got %s" %
-                         (tuple(cmp.shape), tuple(alpha.shape)))
+    who = "matte_compose"
+    n, h, w, nb = _check_frames_and_bg(who, cmp, bg)
+    _check_tensor(who, "alpha", alpha, (torch.float32,), "n,h,w | n,h,w,1", n=n, h=h, w=w)
     nn = 0
     if over:
-        if str(new_bg.dtype).split(".")[-1] != "uint8":
-            raise TypeError("new_bg must be uint8, got %s" % new_bg.dtype)
-        if tuple(new_bg.shape) not in ((n, h, w, 3), (1, h, w, 3), (h, w, 3)):
-            raise ValueError("new_bg must be [n,h,w,3], or one [h,w,3] plate, for cmp %s; got %s" %
-                             (tuple(cmp.shape), tuple(new_bg.shape)))
-        nn = n if tuple(new_bg.shape) == (n, h, w, 3) else 1
-    c = 3 if over else 4
-    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, c)):
-        raise ValueError("matte_compose: out must be uint8 [n,h,w,%d] = %s, got %s %s" %
-                         (c, (n, h, w, c), out.dtype, tuple(out.shape)))
-    for t in (alpha, cmp, bg) + ((new_bg,) if over else ()) + (() if out is None else (out,)):
-        _require_gpu(t)
-        if not t.is_contiguous():
-            raise ValueError("matte_compose: contiguous tensors expected")
-    if out is None:
-        out = torch.empty((n, h, w, c), dtype=torch.uint8, device=cmp.device)
+        shape = _check_tensor(who, "new_bg", new_bg, (torch.uint8,), "n,h,w,3 | 1,h,w,3 | h,w,3", n=n, h=h, w=w)
+        nn = n if shape == (n, h, w, 3) else 1
+    out = _out_or_new(who, "out", out, torch.uint8, "n,h,w,c", cmp.device, ValueError, n=n, h=h, w=w, c=3 if over else 4)
+    for t in (alpha, cmp, bg, new_bg, out):
+        if t is not None:
+            _require_gpu(t)
     check(lib().vm_matte_compose(_ptr(alpha), _ptr(cmp), _ptr(bg), nb, _ptr(new_bg), nn, n, h, w, COMPOSE_MODES[mode],
                                  _ptr(out), stream_handle()), "matte_compose")
     return out
@@ -989,17 +1055,14 @@ def clip_feed(cmp, bg, prev_alpha, backward, forward=None, thresh=15.0, promote=
     the model's dtype — UNetSimple.feed_views returns the pair; ``warped`` f32 [n,h,w] optionally receives a.
     With a forward flow, ``err`` (int32 [1], zeroed by the caller) is set where the reference raises IndexError; when
     ``err`` is None the call keeps a flag of its own, waits for it and raises IndexError itself.  Returns warped."""
-    n, h, w, nb = _check_u8_frames(cmp, bg, None)
+    who = "clip_feed"
+    n, h, w, nb = _check_frames_and_bg(who, cmp, bg)
     if promote not in ("numpy1", "numpy2"):
         raise ValueError("clip_feed: promote must be 'numpy1' or 'numpy2', got %r" % (promote,))
-    for name, t, shapes in (("prev_alpha", prev_alpha, ((n, h, w), (n, h, w, 1))), ("backward", backward, ((n, h, w, 2),)),
-                            ("forward", forward, ((n, h, w, 2),)), ("warped", warped, ((n, h, w), (n, h, w, 1)))):
-        if t is None and name in ("forward", "warped"):
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError("clip_feed: %s must be a float32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
-        if tuple(t.shape) not in shapes:
-            raise ValueError("clip_feed: %s must be %s, got %s" % (name, list(shapes[0]), tuple(t.shape)))
+    for name, t, shapes in (("prev_alpha", prev_alpha, "n,h,w | n,h,w,1"), ("backward", backward, "n,h,w,2"),
+                            ("forward", forward, "n,h,w,2"), ("warped", warped, "n,h,w | n,h,w,1")):
+        if t is not None or name in ("prev_alpha", "backward"):
+            _check_tensor(who, name, t, (torch.float32,), shapes, n=n, h=h, w=w)
     if towers is None or cat is None:
         raise ValueError("clip_feed: towers and cat views are required (UNetSimple.feed_views)")
     if tuple(towers.shape) != (3 * n, h, w, 3) or tuple(cat.shape) != (n, h, w, 9):
@@ -1012,9 +1075,6 @@ def clip_feed(cmp, bg, prev_alpha, backward, forward=None, thresh=15.0, promote=
     for t in (cmp, bg, prev_alpha, backward, forward, towers, cat, warped, err):
         if t is not None:
             _require_gpu(t)
-    for t in (cmp, bg, prev_alpha, backward, forward, warped):
-        if t is not None and not t.is_contiguous():
-            raise ValueError("clip_feed: contiguous frames, mattes and flows expected")
     own = forward is not None and err is None
     if own:
         err = torch.zeros(1, dtype=torch.int32, device=cmp.device)
@@ -1031,45 +1091,26 @@ def clip_feed(cmp, bg, prev_alpha, backward, forward=None, thresh=15.0, promote=
 # ---------------------------------------------------------------- optical flow between two decoded frames
 
 FLOW_DEFAULTS = {"levels": 6, "warps": 3, "iters": 20, "alpha": 15.0}
+FLOW_MODES = ("given", "estimate")  # where a stream's flows come from: its source's items, or its frames
 
 
 def check_flow_options(who, h, w, levels=6, warps=3, iters=20, alpha=15.0):
     """The estimator's shape and options as vm_flow_estimate checks them, on the host -> (levels, warps, iters,
     alpha)."""
-    for name, v in (("levels", levels), ("warps", warps), ("iters", iters)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise TypeError("%s: %s must be an integer, got %r" % (who, name, v))
-        if v < 1:
-            raise ValueError("%s: %s must be at least 1, got %d" % (who, name, v))
+    levels, warps, iters = (check_int(who, name, v, 1) for name, v in (("levels", levels), ("warps", warps),
+                                                                       ("iters", iters)))
     alpha = float(alpha)
     if not alpha > 0.0:
         raise ValueError("%s: alpha must be a positive number, got %r" % (who, alpha))
     if h < 16 or w < 16:
         raise ValueError("%s: frames of at least 16 x 16, got %d x %d" % (who, h, w))
-    return int(levels), int(warps), int(iters), alpha
+    return levels, warps, iters, alpha
 
 
-def _check_flow_frame(who, name, t, shape=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
-    if t.dtype != torch.uint8:
-        raise TypeError("%s: %s must be uint8, got %s" % (who, name, t.dtype))
-    if t.dim() != 3 or t.shape[2] != 3 or (shape is not None and tuple(t.shape) != shape):
-        raise ValueError("%s: %s must be [h,w,3] BGR%s, got %s" % (who, name, "" if shape is None else " = %s" % (shape,),
-                                                                  tuple(t.shape)))
-    if not t.is_contiguous():
-        raise ValueError("%s: %s must be contiguous" % (who, name))
-    return tuple(t.shape)
-
-
-def _flow_buffer(who, name, t, numel, dtype, device):
-    """A caller's contiguous device buffer of at least ``numel`` elements, or a new one."""
-    if t is None:
-        return torch.empty(numel, dtype=dtype, device=device)
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() < numel or not t.is_contiguous():
-        raise ValueError("%s: %s must be a contiguous %s tensor of at least %d elements" % (who, name, dtype, numel))
-    _require_gpu(t)
-    return t
+def flow_options(who, h, w, options):
+    """A dict over FLOW_DEFAULTS (None: the defaults), checked for [h,w] frames -> {"levels": ..., "warps": ...,
+    "iters": ..., "alpha": ...}."""
+    return _options(who, FLOW_DEFAULTS, options, check_flow_options, h, w)
 
 
 def flow_workspace_bytes(h, w, levels=6):
@@ -1083,30 +1124,31 @@ def flow_pyramid_floats(h, w, levels=6):
 def flow_pyramid(frame, levels=6, out=None, work=None):
     """vm_flow_pyramid: the smoothed grey pyramid of one uint8 [h,w,3] BGR frame -> f32 [flow_pyramid_floats(h, w,
     levels)], the levels finest first, each level's start padded to 4 floats."""
-    h, w, _ = _check_flow_frame("flow_pyramid", "frame", frame)
-    levels = check_flow_options("flow_pyramid", h, w, levels)[0]
+    who = "flow_pyramid"
+    h, w, _ = _check_tensor(who, "frame", frame, (torch.uint8,), "h,w,3")
+    levels = check_flow_options(who, h, w, levels)[0]
     _require_gpu(frame)
-    out = _flow_buffer("flow_pyramid", "out", out, flow_pyramid_floats(h, w, levels), torch.float32, frame.device)
-    work = _flow_buffer("flow_pyramid", "work", work, flow_workspace_bytes(h, w, levels), torch.uint8, frame.device)
-    check(lib().vm_flow_pyramid(_ptr(frame), h, w, levels, _ptr(out), _ptr(work), stream_handle()), "flow_pyramid")
+    out = _buffer_or_new(who, "out", out, torch.float32, flow_pyramid_floats(h, w, levels), frame.device)
+    work = _buffer_or_new(who, "work", work, torch.uint8, flow_workspace_bytes(h, w, levels), frame.device)
+    check(lib().vm_flow_pyramid(_ptr(frame), h, w, levels, _ptr(out), _ptr(work), stream_handle()), who)
     return out
 
 
 def flow_from_pyramids(cur, prev, h, w, levels=6, warps=3, iters=20, alpha=15.0, out=None, work=None):
     """vm_flow_from_pyramids: the flow of estimate_flow from two flow_pyramid results of [h,w] frames."""
-    levels, warps, iters, alpha = check_flow_options("flow_from_pyramids", h, w, levels, warps, iters, alpha)
-    for t in (cur, prev):
+    who = "flow_from_pyramids"
+    levels, warps, iters, alpha = check_flow_options(who, h, w, levels, warps, iters, alpha)
+    for t in (cur, prev):  # (buffers whose size is the library's to tell: the device first)
         _require_gpu(t)
     n = flow_pyramid_floats(h, w, levels)
-    cur = _flow_buffer("flow_from_pyramids", "cur", cur, n, torch.float32, cur.device)
-    prev = _flow_buffer("flow_from_pyramids", "prev", prev, n, torch.float32, cur.device)
-    if out is not None and tuple(out.shape) != (h, w, 2):
-        raise ValueError("flow_from_pyramids: out must be [h,w,2] = %s, got %s" % ((h, w, 2), tuple(out.shape)))
-    out = _flow_buffer("flow_from_pyramids", "out", out, h * w * 2, torch.float32, cur.device)
-    work = _flow_buffer("flow_from_pyramids", "work", work, flow_workspace_bytes(h, w, levels), torch.uint8, cur.device)
+    cur = _buffer_or_new(who, "cur", cur, torch.float32, n, cur.device)
+    prev = _buffer_or_new(who, "prev", prev, torch.float32, n, cur.device)
+    out = _out_or_new(who, "out", out, torch.float32, "h,w,2", cur.device, ValueError, h=h, w=w)
+    _require_gpu(out)
+    work = _buffer_or_new(who, "work", work, torch.uint8, flow_workspace_bytes(h, w, levels), cur.device)
     check(lib().vm_flow_from_pyramids(_ptr(cur), _ptr(prev), h, w, levels, warps, iters, alpha, _ptr(out), _ptr(work),
-                                      stream_handle()), "flow_from_pyramids")
-    return out.view(h, w, 2)
+                                      stream_handle()), who)
+    return out
 
 
 def estimate_flow(cur_u8, prev_u8, levels=6, warps=3, iters=20, alpha=15.0, out=None, work=None):
@@ -1115,19 +1157,17 @@ def estimate_flow(cur_u8, prev_u8, levels=6, warps=3, iters=20, alpha=15.0, out=
     forward flow is estimate_flow(prev, cur)).  Coarse-to-fine Horn-Schunck with warping, f32 (include/vmatting.h).
     ``out``: a contiguous f32 [h,w,2] device tensor; ``work``: a uint8 device buffer of flow_workspace_bytes(h, w,
     levels); both are allocated when None."""
-    shape = _check_flow_frame("estimate_flow", "cur", cur_u8)
-    _check_flow_frame("estimate_flow", "prev", prev_u8, shape)
-    h, w, _ = shape
-    levels, warps, iters, alpha = check_flow_options("estimate_flow", h, w, levels, warps, iters, alpha)
-    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (h, w, 2)):
-        raise ValueError("estimate_flow: out must be [h,w,2] = %s, got %s" % ((h, w, 2), tuple(getattr(out, "shape", ()))))
-    _require_gpu(cur_u8)
-    _require_gpu(prev_u8)
-    out = _flow_buffer("estimate_flow", "out", out, h * w * 2, torch.float32, cur_u8.device)
-    work = _flow_buffer("estimate_flow", "work", work, flow_workspace_bytes(h, w, levels), torch.uint8, cur_u8.device)
+    who = "estimate_flow"
+    h, w, _ = _check_tensor(who, "cur", cur_u8, (torch.uint8,), "h,w,3")
+    _check_tensor(who, "prev", prev_u8, (torch.uint8,), "h,w,3", h=h, w=w)
+    levels, warps, iters, alpha = check_flow_options(who, h, w, levels, warps, iters, alpha)
+    out = _out_or_new(who, "out", out, torch.float32, "h,w,2", cur_u8.device, ValueError, h=h, w=w)
+    for t in (cur_u8, prev_u8, out):
+        _require_gpu(t)
+    work = _buffer_or_new(who, "work", work, torch.uint8, flow_workspace_bytes(h, w, levels), cur_u8.device)
     check(lib().vm_flow_estimate(_ptr(cur_u8), _ptr(prev_u8), h, w, levels, warps, iters, alpha, _ptr(out), _ptr(work),
-                                 stream_handle()), "estimate_flow")
-    return out.view(h, w, 2)
+                                 stream_handle()), who)
+    return out
 
 
 # ---------------------------------------------------------------- trimap propagation by optical flow
@@ -1137,11 +1177,7 @@ GROW_MAX = 8
 
 def check_grow(who, grow):
     """``grow`` as vm_trimap_propagate checks it, on the host: an integer in 0..8."""
-    if isinstance(grow, bool) or not isinstance(grow, (int, np.integer)):
-        raise TypeError("%s: grow must be an integer, got %r" % (who, grow))
-    if not 0 <= grow <= GROW_MAX:
-        raise ValueError("%s: grow must be in 0..%d, got %d" % (who, GROW_MAX, grow))
-    return int(grow)
+    return check_int(who, "grow", grow, 0, GROW_MAX)
 
 
 def trimap_propagate_workspace_bytes(h, w, grow):
@@ -1156,29 +1192,15 @@ def trimap_propagate(prev, flow, grow=1, out=None, work=None):
     uint8 [h,w] device tensor that is not ``prev``; ``work``: a uint8 device buffer of
     trimap_propagate_workspace_bytes(h, w, grow); both are allocated when None."""
     who = "trimap_propagate"
-    for name, t, dt in (("prev", prev, torch.uint8), ("flow", flow, torch.float32)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
-        if t.dtype != dt:
-            raise TypeError("%s: %s must be %s, got %s" % (who, name, dt, t.dtype))
-    if prev.dim() != 2 or prev.shape[0] < 1 or prev.shape[1] < 1:
-        raise ValueError("%s: prev must be [h,w], got %s" % (who, tuple(prev.shape)))
-    h, w = (int(v) for v in prev.shape)
-    if tuple(flow.shape) != (h, w, 2):
-        raise ValueError("%s: flow must be [h,w,2] = %s, got %s" % (who, (h, w, 2), tuple(flow.shape)))
-    for name, t in (("prev", prev), ("flow", flow)):
-        if not t.is_contiguous():
-            raise ValueError("%s: %s must be contiguous" % (who, name))
+    h, w = _check_tensor(who, "prev", prev, (torch.uint8,), "h,w")
+    _check_tensor(who, "flow", flow, (torch.float32,), "h,w,2", h=h, w=w)
+    grow = check_int(who, "grow", grow)  # (its range is the library's check: the size query gives 0 outside it)
+    out = _out_or_new(who, "out", out, torch.uint8, "h,w", prev.device, ValueError, h=h, w=w)
+    for t in (prev, flow, out):
         _require_gpu(t)
-    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (h, w)):
-        raise ValueError("%s: out must be [h,w] = %s, got %s" % (who, (h, w), tuple(getattr(out, "shape", ()))))
-    out = _flow_buffer(who, "out", out, h * w, torch.uint8, prev.device)
-    if isinstance(grow, bool) or not isinstance(grow, (int, np.integer)):
-        raise TypeError("%s: grow must be an integer, got %r" % (who, grow))
-    grow = int(grow)  # (its range is the library's check: the size query gives 0 outside it)
-    work = _flow_buffer(who, "work", work, trimap_propagate_workspace_bytes(h, w, grow), torch.uint8, prev.device)
+    work = _buffer_or_new(who, "work", work, torch.uint8, trimap_propagate_workspace_bytes(h, w, grow), prev.device)
     check(lib().vm_trimap_propagate(_ptr(prev), _ptr(flow), h, w, grow, _ptr(out), _ptr(work), stream_handle()), who)
-    return out.view(h, w)
+    return out
 
 
 # ---------------------------------------------------------------- trimaps from the background plate
@@ -1191,15 +1213,17 @@ PLATE_LEVEL_MAX, PLATE_RADIUS_MAX = 442, 32
 def check_plate_options(who, lo, hi, r_bg, r_fg):
     """The options of vm_trimap_from_plate as it checks them, on the host: integers with 0 <= lo < hi <= 442 and radii
     in 0..32 -> (lo, hi, r_bg, r_fg)."""
-    for name, v in (("lo", lo), ("hi", hi), ("r_bg", r_bg), ("r_fg", r_fg)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise TypeError("%s: %s must be an integer, got %r" % (who, name, v))
+    lo, hi, r_bg, r_fg = (check_int(who, name, v) for name, v in (("lo", lo), ("hi", hi), ("r_bg", r_bg), ("r_fg", r_fg)))
     if not 0 <= lo < hi <= PLATE_LEVEL_MAX:
         raise ValueError("%s: 0 <= lo < hi <= %d expected, got lo %d, hi %d" % (who, PLATE_LEVEL_MAX, lo, hi))
     for name, v in (("r_bg", r_bg), ("r_fg", r_fg)):
-        if not 0 <= v <= PLATE_RADIUS_MAX:
-            raise ValueError("%s: %s must be in 0..%d, got %d" % (who, name, PLATE_RADIUS_MAX, v))
-    return int(lo), int(hi), int(r_bg), int(r_fg)
+        check_int(who, name, v, 0, PLATE_RADIUS_MAX)
+    return lo, hi, r_bg, r_fg
+
+
+def plate_options(who, options):
+    """A dict over PLATE_DEFAULTS (None: the defaults), checked -> {"lo": lo, "hi": hi, "r_bg": r_bg, "r_fg": r_fg}."""
+    return _options(who, PLATE_DEFAULTS, options, check_plate_options)
 
 
 def trimap_from_plate_workspace_bytes(n, h, w):
@@ -1214,39 +1238,18 @@ def trimap_from_plate(cmp, bg, lo=PLATE_DEFAULTS["lo"], hi=PLATE_DEFAULTS["hi"],
     128 elsewhere (include/vmatting.h).  ``out``: a contiguous uint8 [n,h,w] device tensor; ``work``: a uint8 device
     buffer of trimap_from_plate_workspace_bytes(n, h, w); both are allocated when None."""
     who = "trimap_from_plate"
-    for name, t in (("cmp", cmp), ("bg", bg)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
-    n, h, w, nb = _check_u8_frames(cmp, bg, None)
+    n, h, w, nb = _check_frames_and_bg(who, cmp, bg)
     lo, hi, r_bg, r_fg = check_plate_options(who, lo, hi, r_bg, r_fg)
-    for name, t in (("cmp", cmp), ("bg", bg)):
-        if not t.is_contiguous():
-            raise ValueError("%s: %s must be contiguous" % (who, name))
+    out = _out_or_new(who, "out", out, torch.uint8, "n,h,w", cmp.device, ValueError, n=n, h=h, w=w)
+    for t in (cmp, bg, out):
         _require_gpu(t)
-    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, h, w)):
-        raise ValueError("%s: out must be [n,h,w] = %s, got %s" % (who, (n, h, w), tuple(getattr(out, "shape", ()))))
-    out = _flow_buffer(who, "out", out, n * h * w, torch.uint8, cmp.device)
-    work = _flow_buffer(who, "work", work, trimap_from_plate_workspace_bytes(n, h, w), torch.uint8, cmp.device)
+    work = _buffer_or_new(who, "work", work, torch.uint8, trimap_from_plate_workspace_bytes(n, h, w), cmp.device)
     check(lib().vm_trimap_from_plate(_ptr(cmp), _ptr(bg), nb, n, h, w, lo, hi, r_bg, r_fg, _ptr(out), _ptr(work),
                                      stream_handle()), who)
-    return out.view(n, h, w)
+    return out
 
 
 # ---------------------------------------------------------------- connected components, and enclosed background
-
-def _check_u8_stack(who, name, t):
-    """A contiguous uint8 [n,h,w] device tensor -> (n, h, w)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
-    if t.dtype != torch.uint8:
-        raise TypeError("%s: %s must be uint8, got %s" % (who, name, t.dtype))
-    if t.dim() != 3 or min(t.shape) < 1:
-        raise ValueError("%s: %s must be [n,h,w], got %s" % (who, name, tuple(t.shape)))
-    if not t.is_contiguous():
-        raise ValueError("%s: %s must be contiguous" % (who, name))
-    _require_gpu(t)
-    return tuple(int(v) for v in t.shape)
-
 
 def label_components(mask, value=0, connectivity=4, out=None):
     """vm_components_label: the connected components of the pixels of ``mask`` (uint8 [n,h,w]) whose byte equals
@@ -1254,19 +1257,15 @@ def label_components(mask, value=0, connectivity=4, out=None):
     or 8-connected component; -1 for every other pixel (include/vmatting.h).  ``out``: a contiguous int32 [n,h,w] device
     tensor, allocated when None."""
     who = "label_components"
-    n, h, w = _check_u8_stack(who, "mask", mask)
-    for name, v in (("value", value), ("connectivity", connectivity)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise TypeError("%s: %s must be an integer, got %r" % (who, name, v))
-    if not 0 <= value <= 255:
-        raise ValueError("%s: value must be in 0..255, got %d" % (who, value))
+    n, h, w = _check_tensor(who, "mask", mask, (torch.uint8,), "n,h,w")
+    value, connectivity = check_int(who, "value", value, 0, 255), check_int(who, "connectivity", connectivity)
     if connectivity not in (4, 8):
         raise ValueError("%s: connectivity must be 4 or 8, got %d" % (who, connectivity))
-    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, h, w)):
-        raise ValueError("%s: out must be [n,h,w] = %s, got %s" % (who, (n, h, w), tuple(getattr(out, "shape", ()))))
-    out = _flow_buffer(who, "out", out, n * h * w, torch.int32, mask.device)
-    check(lib().vm_components_label(_ptr(mask), n, h, w, int(value), int(connectivity), _ptr(out), stream_handle()), who)
-    return out.view(n, h, w)
+    out = _out_or_new(who, "out", out, torch.int32, "n,h,w", mask.device, ValueError, n=n, h=h, w=w)
+    for t in (mask, out):
+        _require_gpu(t)
+    check(lib().vm_components_label(_ptr(mask), n, h, w, value, connectivity, _ptr(out), stream_handle()), who)
+    return out
 
 
 def check_fill(who, fill):
@@ -1276,9 +1275,11 @@ def check_fill(who, fill):
         return None
     if fill is True:
         return 0
-    if isinstance(fill, (int, np.integer)) and not isinstance(fill, (bool, np.bool_)) and fill >= 1:
-        return int(fill)
-    raise ValueError("%s: fill is None / False (off), True (any area) or an integer area cap >= 1, got %r" % (who, fill))
+    try:
+        return check_int(who, "fill", fill, 1)
+    except (TypeError, ValueError):
+        raise ValueError("%s: fill is None / False (off), True (any area) or an integer area cap >= 1, got %r" %
+                         (who, fill)) from None
 
 
 def trimap_fill_enclosed_workspace_bytes(n, h, w):
@@ -1292,18 +1293,14 @@ def trimap_fill_enclosed(trimap, max_area=0, out=None, work=None):
     itself fills in place.  ``work``: a uint8 device buffer of trimap_fill_enclosed_workspace_bytes(n, h, w), allocated
     when None."""
     who = "trimap_fill_enclosed"
-    n, h, w = _check_u8_stack(who, "trimap", trimap)
-    if isinstance(max_area, bool) or not isinstance(max_area, (int, np.integer)):
-        raise TypeError("%s: max_area must be an integer, got %r" % (who, max_area))
-    if max_area < 0:
-        raise ValueError("%s: max_area must be 0 (any area) or a cap >= 1, got %d" % (who, max_area))
-    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, h, w)):
-        raise ValueError("%s: out must be [n,h,w] = %s, got %s" % (who, (n, h, w), tuple(getattr(out, "shape", ()))))
-    out = _flow_buffer(who, "out", out, n * h * w, torch.uint8, trimap.device)
-    work = _flow_buffer(who, "work", work, trimap_fill_enclosed_workspace_bytes(n, h, w), torch.uint8, trimap.device)
-    check(lib().vm_trimap_fill_enclosed(_ptr(trimap), n, h, w, int(max_area), _ptr(out), _ptr(work), stream_handle()),
-          who)
-    return out.view(n, h, w)
+    n, h, w = _check_tensor(who, "trimap", trimap, (torch.uint8,), "n,h,w")
+    max_area = check_int(who, "max_area", max_area, 0)
+    out = _out_or_new(who, "out", out, torch.uint8, "n,h,w", trimap.device, ValueError, n=n, h=h, w=w)
+    for t in (trimap, out):
+        _require_gpu(t)
+    work = _buffer_or_new(who, "work", work, torch.uint8, trimap_fill_enclosed_workspace_bytes(n, h, w), trimap.device)
+    check(lib().vm_trimap_fill_enclosed(_ptr(trimap), n, h, w, max_area, _ptr(out), _ptr(work), stream_handle()), who)
+    return out
 
 
 # ---------------------------------------------------------------- the background plate from the clip itself
@@ -1319,34 +1316,17 @@ def plate_from_samples(samples, plate=None, spread=None, want_spread=True):
     tensors of those shapes, allocated when None; with ``want_spread`` False no spread is computed and (plate, None)
     returned."""
     who = "plate_from_samples"
-    for name, t in (("samples", samples), ("plate", plate), ("spread", spread)):
-        if t is None and name != "samples":
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
-        if t.dtype != torch.uint8:
-            raise TypeError("%s: %s must be uint8, got %s" % (who, name, t.dtype))
-    if samples.dim() != 4 or samples.shape[3] != 3 or min(samples.shape) < 1:
-        raise ValueError("%s: samples must be [n,h,w,3] BGR, got %s" % (who, tuple(samples.shape)))
-    n, h, w, _ = (int(v) for v in samples.shape)
+    n, h, w, _ = _check_tensor(who, "samples", samples, (torch.uint8,), "n,h,w,3")
     if n > PLATE_MAX_SAMPLES:
         raise ValueError("%s: at most %d samples, got %d" % (who, PLATE_MAX_SAMPLES, n))
     if spread is not None and not want_spread:
         raise ValueError("%s: a spread buffer although want_spread is False" % who)
-    for name, t, shape in (("samples", samples, (n, h, w, 3)), ("plate", plate, (h, w, 3)), ("spread", spread, (h, w))):
-        if t is None:
-            continue
-        if tuple(t.shape) != shape:
-            raise ValueError("%s: %s must be %s, got %s" % (who, name, shape, tuple(t.shape)))
-        if not t.is_contiguous():
-            raise ValueError("%s: %s must be contiguous" % (who, name))
+    plate = _out_or_new(who, "plate", plate, torch.uint8, "h,w,3", samples.device, h=h, w=w)
+    if want_spread:
+        spread = _out_or_new(who, "spread", spread, torch.uint8, "h,w", samples.device, h=h, w=w)
     for t in (samples, plate, spread):
         if t is not None:
             _require_gpu(t)
-    if plate is None:
-        plate = torch.empty((h, w, 3), dtype=torch.uint8, device=samples.device)
-    if spread is None and want_spread:
-        spread = torch.empty((h, w), dtype=torch.uint8, device=samples.device)
     check(lib().vm_plate_from_samples(_ptr(samples), n, h, w, _ptr(plate), _ptr(spread), stream_handle()), who)
     return plate, spread
 
@@ -1360,18 +1340,6 @@ def matte_score_workspace_bytes(n, h, w):
     return lib().vm_matte_score_workspace_bytes(n, h, w)
 
 
-def _score_plane(who, name, t, shape, dtypes):
-    """A contiguous torch tensor of ``shape`` and one of ``dtypes``, checked on the host (its device is checked last)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
-    if t.dtype not in dtypes:
-        raise TypeError("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError("%s: %s must be %s, got %s" % (who, name, list(shape), tuple(t.shape)))
-    if not t.is_contiguous():
-        raise ValueError("%s: %s must be contiguous" % (who, name))
-
-
 def matte_score(pred, gt, trimap=None, prev=None, backward=None, out=None, grad_map=None, work=None):
     """vm_matte_score: the sums behind SAD, MSE, gradient error, dtSSD and MESSDdt of ``pred`` against ``gt`` (each
     [n,h,w], f32 or uint8 independently; an f32 value is clamped to [0,1], a uint8 is q / 255) -> f64 [n,8], row j =
@@ -1383,35 +1351,25 @@ def matte_score(pred, gt, trimap=None, prev=None, backward=None, out=None, grad_
     ``grad_map`` f32 [n,h,w] (receives the gradient error of every pixel), ``work`` a uint8 buffer of
     matte_score_workspace_bytes(n, h, w): contiguous device tensors; out and work are allocated when None."""
     who = "matte_score"
-    if not isinstance(pred, torch.Tensor):
-        raise TypeError("%s: pred must be a torch tensor, got %s" % (who, type(pred).__name__))
-    if pred.dim() != 3 or min(pred.shape) < 1:
-        raise ValueError("%s: pred must be [n,h,w], got %s" % (who, tuple(pred.shape)))
-    n, h, w = (int(v) for v in pred.shape)
-    mattes = tuple(_SCORE_DT)
-    _score_plane(who, "pred", pred, (n, h, w), mattes)
-    _score_plane(who, "gt", gt, (n, h, w), mattes)
-    if trimap is not None:
-        _score_plane(who, "trimap", trimap, (n, h, w), (torch.uint8,))
+    n, h, w = _check_tensor(who, "pred", pred, tuple(_SCORE_DT), "n,h,w")
+    dims = {"n": n, "h": h, "w": w}
+    _check_tensor(who, "gt", gt, tuple(_SCORE_DT), "n,h,w", **dims)
     pp = pg = None
     if prev is not None:
         if not isinstance(prev, (tuple, list)) or len(prev) != 2:
             raise TypeError("%s: prev must be the pair (prev_pred, prev_gt)" % who)
         pp, pg = prev
-        _score_plane(who, "prev_pred", pp, (h, w), (pred.dtype,))
-        _score_plane(who, "prev_gt", pg, (h, w), (gt.dtype,))
-    if backward is not None:
-        _score_plane(who, "backward", backward, (n, h, w, 2), (torch.float32,))
-    if out is not None:
-        _score_plane(who, "out", out, (n, 8), (torch.float64,))
-    if grad_map is not None:
-        _score_plane(who, "grad_map", grad_map, (n, h, w), (torch.float32,))
+        _check_tensor(who, "prev_pred", pp, (pred.dtype,), "h,w", **dims)
+        _check_tensor(who, "prev_gt", pg, (gt.dtype,), "h,w", **dims)
+    for name, t, dtype, shape in (("trimap", trimap, torch.uint8, "n,h,w"), ("backward", backward, torch.float32, "n,h,w,2"),
+                                  ("grad_map", grad_map, torch.float32, "n,h,w")):
+        if t is not None:
+            _check_tensor(who, name, t, (dtype,), shape, **dims)
+    out = _out_or_new(who, "out", out, torch.float64, "n,8", pred.device, n=n)
     for t in (pred, gt, trimap, pp, pg, backward, out, grad_map):
         if t is not None:
             _require_gpu(t)
-    if out is None:
-        out = torch.empty((n, 8), dtype=torch.float64, device=pred.device)
-    work = _flow_buffer(who, "work", work, matte_score_workspace_bytes(n, h, w), torch.uint8, pred.device)
+    work = _buffer_or_new(who, "work", work, torch.uint8, matte_score_workspace_bytes(n, h, w), pred.device)
     check(lib().vm_matte_score(_ptr(pred), _SCORE_DT[pred.dtype], _ptr(gt), _SCORE_DT[gt.dtype], _ptr(trimap), _ptr(pp),
                                _ptr(pg), _ptr(backward), n, h, w, _ptr(out), _ptr(grad_map), _ptr(work),
                                stream_handle()), who)
@@ -1466,11 +1424,7 @@ GUIDED_R_MAX, GUIDED_EPS_MIN, GUIDED_EPS_MAX = 8, 1e-5, 1.0
 
 def check_scale(who, scale, smallest=2):
     """The reduction factor: an integer in ``smallest``..4 (an op takes 2..4; FrameStream also 1: no reduction)."""
-    if isinstance(scale, (bool, np.bool_)) or not isinstance(scale, (int, np.integer)):
-        raise TypeError("%s: scale must be an integer, got %r" % (who, scale))
-    if not smallest <= scale <= SCALES[-1]:
-        raise ValueError("%s: scale must be in %d..%d, got %d" % (who, smallest, SCALES[-1], scale))
-    return int(scale)
+    return check_int(who, "scale", scale, smallest, SCALES[-1])
 
 
 def reduced_size(h, w, scale):
@@ -1481,25 +1435,17 @@ def reduced_size(h, w, scale):
 def check_guided_options(who, r=GUIDED_DEFAULTS["r"], eps=GUIDED_DEFAULTS["eps"]):
     """The options of vm_guided_coeffs as it checks them, on the host: an integer r in 1..8 and a real eps in
     [1e-5, 1] -> (r, eps)."""
-    if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, np.integer)):
-        raise TypeError("%s: r must be an integer, got %r" % (who, r))
-    if isinstance(eps, (bool, np.bool_)) or not isinstance(eps, (int, float, np.integer, np.floating)):
+    r = check_int(who, "r", r, 1, GUIDED_R_MAX)
+    if not isinstance(eps, (int, float, np.integer, np.floating)) or isinstance(eps, (bool, np.bool_)):
         raise TypeError("%s: eps must be a real number, got %r" % (who, eps))
-    if not 1 <= r <= GUIDED_R_MAX:
-        raise ValueError("%s: r must be in 1..%d, got %d" % (who, GUIDED_R_MAX, r))
     if not GUIDED_EPS_MIN <= eps <= GUIDED_EPS_MAX:  # (false for NaN)
         raise ValueError("%s: eps must be in [%g, %g], got %r" % (who, GUIDED_EPS_MIN, GUIDED_EPS_MAX, eps))
-    return int(r), float(eps)
+    return r, float(eps)
 
 
 def guided_options(who, options):
     """A dict over GUIDED_DEFAULTS (None: the defaults), checked -> {"r": r, "eps": eps}."""
-    opts = dict(GUIDED_DEFAULTS)
-    for k, v in dict(options or {}).items():
-        if k not in opts:
-            raise ValueError("%s: guided options are %s, got %r" % (who, sorted(opts), k))
-        opts[k] = v
-    return dict(zip(("r", "eps"), check_guided_options(who, **opts)))
+    return _options(who, GUIDED_DEFAULTS, options, check_guided_options)
 
 
 def frames_reduce_u8(frames, scale, kind="mean", out=None):
@@ -1513,24 +1459,11 @@ def frames_reduce_u8(frames, scale, kind="mean", out=None):
         raise ValueError("%s: kind must be one of %s, got %r" % (who, sorted(REDUCE_KINDS), kind))
     code, c = REDUCE_KINDS[kind]
     scale = check_scale(who, scale)
-    if not isinstance(frames, torch.Tensor):
-        raise TypeError("%s: frames must be a torch tensor, got %s" % (who, type(frames).__name__))
-    if frames.dtype != torch.uint8:
-        raise TypeError("%s: frames must be uint8, got %s" % (who, frames.dtype))
-    want = "[n,h,w,3]" if c == 3 else "[n,h,w]"
-    if frames.dim() != (4 if c == 3 else 3) or min(frames.shape) < 1 or (c == 3 and frames.shape[3] != 3):
-        raise ValueError("%s: kind %r takes %s frames, got %s" % (who, kind, want, tuple(frames.shape)))
-    if not frames.is_contiguous():
-        raise ValueError("%s: frames must be contiguous" % who)
-    n, h, w = (int(v) for v in frames.shape[:3])
+    n, h, w = _check_tensor(who, "frames", frames, (torch.uint8,), "n,h,w,3" if c == 3 else "n,h,w")[:3]
     hm, wm = reduced_size(h, w, scale)
-    shape = (n, hm, wm) + ((3,) if c == 3 else ())
-    if out is not None:
-        _score_plane(who, "out", out, shape, (torch.uint8,))
-    _require_gpu(frames)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
-    _require_gpu(out)
+    out = _out_or_new(who, "out", out, torch.uint8, "n,hm,wm,3" if c == 3 else "n,hm,wm", frames.device, n=n, hm=hm, wm=wm)
+    for t in (frames, out):
+        _require_gpu(t)
     check(lib().vm_frames_reduce_u8(_ptr(frames), n, h, w, c, scale, code, _ptr(out), stream_handle()), who)
     return out
 
@@ -1546,24 +1479,13 @@ def guided_coeffs(guide_lo, alpha_lo, r=GUIDED_DEFAULTS["r"], eps=GUIDED_DEFAULT
     (include/vmatting.h).  ``out``: a contiguous f32 [n,hm,wm,4] device tensor; ``work``: a uint8 device buffer of
     guided_workspace_bytes(n, hm, wm); both are allocated when None."""
     who = "guided_coeffs"
-    if not isinstance(guide_lo, torch.Tensor):
-        raise TypeError("%s: guide_lo must be a torch tensor, got %s" % (who, type(guide_lo).__name__))
-    if guide_lo.dim() != 4 or guide_lo.shape[3] != 3 or min(guide_lo.shape) < 1:
-        raise ValueError("%s: guide_lo must be [n,hm,wm,3], got %s" % (who, tuple(guide_lo.shape)))
-    n, hm, wm = (int(v) for v in guide_lo.shape[:3])
-    _score_plane(who, "guide_lo", guide_lo, (n, hm, wm, 3), (torch.uint8,))
-    if not isinstance(alpha_lo, torch.Tensor):
-        raise TypeError("%s: alpha_lo must be a torch tensor, got %s" % (who, type(alpha_lo).__name__))
-    _score_plane(who, "alpha_lo", alpha_lo, (n, hm, wm, 1) if alpha_lo.dim() == 4 else (n, hm, wm), (torch.float32,))
+    n, hm, wm, _ = _check_tensor(who, "guide_lo", guide_lo, (torch.uint8,), "n,hm,wm,3")
+    _check_tensor(who, "alpha_lo", alpha_lo, (torch.float32,), "n,hm,wm | n,hm,wm,1", n=n, hm=hm, wm=wm)
     r, eps = check_guided_options(who, r, eps)
-    if out is not None:
-        _score_plane(who, "out", out, (n, hm, wm, 4), (torch.float32,))
+    out = _out_or_new(who, "out", out, torch.float32, "n,hm,wm,4", guide_lo.device, n=n, hm=hm, wm=wm)
     for t in (guide_lo, alpha_lo, out):
-        if t is not None:
-            _require_gpu(t)
-    if out is None:
-        out = torch.empty((n, hm, wm, 4), dtype=torch.float32, device=guide_lo.device)
-    work = _flow_buffer(who, "work", work, guided_workspace_bytes(n, hm, wm), torch.uint8, guide_lo.device)
+        _require_gpu(t)
+    work = _buffer_or_new(who, "work", work, torch.uint8, guided_workspace_bytes(n, hm, wm), guide_lo.device)
     check(lib().vm_guided_coeffs(_ptr(guide_lo), _ptr(alpha_lo), n, hm, wm, r, eps, _ptr(out), _ptr(work),
                                  stream_handle()), who)
     return out
@@ -1576,25 +1498,12 @@ def guided_apply(ab, guide_hi, scale, out=None):
     (include/vmatting.h).  ``out``: a contiguous f32 [n,h,w,1] or [n,h,w] device tensor, allocated when None."""
     who = "guided_apply"
     scale = check_scale(who, scale)
-    if not isinstance(guide_hi, torch.Tensor):
-        raise TypeError("%s: guide_hi must be a torch tensor, got %s" % (who, type(guide_hi).__name__))
-    if guide_hi.dim() != 4 or guide_hi.shape[3] != 3 or min(guide_hi.shape) < 1:
-        raise ValueError("%s: guide_hi must be [n,h,w,3], got %s" % (who, tuple(guide_hi.shape)))
-    n, h, w = (int(v) for v in guide_hi.shape[:3])
-    _score_plane(who, "guide_hi", guide_hi, (n, h, w, 3), (torch.uint8,))
+    n, h, w, _ = _check_tensor(who, "guide_hi", guide_hi, (torch.uint8,), "n,h,w,3")
     hm, wm = reduced_size(h, w, scale)
-    if not isinstance(ab, torch.Tensor):
-        raise TypeError("%s: ab must be a torch tensor, got %s" % (who, type(ab).__name__))
-    _score_plane(who, "ab", ab, (n, hm, wm, 4), (torch.float32,))
-    if out is not None:
-        if not isinstance(out, torch.Tensor):
-            raise TypeError("%s: out must be a torch tensor, got %s" % (who, type(out).__name__))
-        _score_plane(who, "out", out, (n, h, w) if out.dim() == 3 else (n, h, w, 1), (torch.float32,))
+    _check_tensor(who, "ab", ab, (torch.float32,), "n,hm,wm,4", n=n, hm=hm, wm=wm)
+    out = _out_or_new(who, "out", out, torch.float32, "n,h,w,1 | n,h,w", guide_hi.device, n=n, h=h, w=w)
     for t in (ab, guide_hi, out):
-        if t is not None:
-            _require_gpu(t)
-    if out is None:
-        out = torch.empty((n, h, w, 1), dtype=torch.float32, device=guide_hi.device)
+        _require_gpu(t)
     check(lib().vm_guided_apply(_ptr(ab), _ptr(guide_hi), n, h, w, scale, _ptr(out), stream_handle()), who)
     return out
 

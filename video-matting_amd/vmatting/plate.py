@@ -14,15 +14,9 @@ It needs a locked-off camera.  A pixel that the subject covers in more than half
 
 import numpy as np
 
+from .ops import check_int
+
 CAPACITY_MAX = 64  # ops.PLATE_MAX_SAMPLES, VM_PLATE_MAX_SAMPLES
-
-
-def _integer(who, name, v, lo, hi=None):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise TypeError("%s: %s must be an integer, got %r" % (who, name, v))
-    if v < lo or (hi is not None and v > hi):
-        raise ValueError("%s: %s must be %s, got %d" % (who, name, ">= %d" % lo if hi is None else "in %d..%d" % (lo, hi), v))
-    return int(v)
 
 
 class SampleSchedule:
@@ -36,10 +30,10 @@ class SampleSchedule:
     (capacity, every, frames seen), between capacity / 2 and capacity of them once the clip is that long."""
 
     def __init__(self, capacity=64, every=1):
-        self.capacity = _integer("SampleSchedule", "capacity", capacity, 2, CAPACITY_MAX)
+        self.capacity = check_int("SampleSchedule", "capacity", capacity, 2, CAPACITY_MAX)
         if self.capacity % 2:
             raise ValueError("SampleSchedule: capacity must be even, got %d" % capacity)
-        self.every = _integer("SampleSchedule", "every", every, 1)
+        self.every = check_int("SampleSchedule", "every", every, 1)
         self.reset()
 
     def reset(self):
@@ -75,7 +69,7 @@ class PlateEstimator:
     one uint8 [capacity,h,w,3] device buffer, ``result`` is ops.plate_from_samples of those kept."""
 
     def __init__(self, h, w, capacity=64, every=1, device=None):
-        self.h, self.w = _integer("PlateEstimator", "h", h, 1), _integer("PlateEstimator", "w", w, 1)
+        self.h, self.w = check_int("PlateEstimator", "h", h, 1), check_int("PlateEstimator", "w", w, 1)
         self.schedule = SampleSchedule(capacity, every)
         self.device = device
         self._buf = None  # allocated by the first add

@@ -163,16 +163,13 @@ def fill_enclosed(trimap_u8, max_area=0):
         raise TypeError("%s: the trimap must be uint8, got %s" % (who, trimap_u8.dtype))
     if len(trimap_u8.shape) not in (2, 3) or min(trimap_u8.shape) < 1:
         raise ValueError("%s: the trimap must be [H,W] or [N,H,W], got %s" % (who, tuple(trimap_u8.shape)))
-    if isinstance(max_area, bool) or not isinstance(max_area, (int, np.integer)):
-        raise TypeError("%s: max_area must be an integer, got %r" % (who, max_area))
-    if max_area < 0:
-        raise ValueError("%s: max_area must be 0 (any area) or a cap >= 1, got %d" % (who, max_area))
+    max_area = ops.check_int(who, "max_area", max_area, 0)
     single = len(trimap_u8.shape) == 2
     tri = trimap_u8[None] if single else trimap_u8
     if device:
-        out = ops.trimap_fill_enclosed(tri.contiguous(), int(max_area))
+        out = ops.trimap_fill_enclosed(tri.contiguous(), max_area)
     else:
-        out = ops.trimap_fill_enclosed(torch.from_numpy(tri).cuda(), int(max_area)).cpu().numpy()
+        out = ops.trimap_fill_enclosed(torch.from_numpy(tri).cuda(), max_area).cpu().numpy()
     return out[0] if single else out
 
 
@@ -191,8 +188,7 @@ def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, 
     if isinstance(cmp_u8, torch.Tensor) != isinstance(bg_u8, torch.Tensor):
         raise TypeError("%s: cmp and bg are both numpy arrays or both torch tensors" % who)
     given = {"lo": lo, "hi": hi, "r_bg": r_bg, "r_fg": r_fg}
-    opts = dict(ops.PLATE_DEFAULTS, **{k: v for k, v in given.items() if v is not None})
-    ops.check_plate_options(who, **opts)
+    opts = ops.plate_options(who, {k: v for k, v in given.items() if v is not None})
     device = isinstance(cmp_u8, torch.Tensor)
     if not device:
         cmp_u8, bg_u8 = np.ascontiguousarray(cmp_u8), np.ascontiguousarray(bg_u8)

@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 
-FLOW_MODES = (None, "given", "estimate")
+FLOW_MODES = (None,) + ops.FLOW_MODES
 
 
 def _dtype_of(a):
@@ -37,28 +37,18 @@ class MatteScorer:
     its levels / warps / iters / alpha), one pyramid per frame shared by the two pairs it belongs to."""
 
     def __init__(self, h, w, device="cuda", flow=None, flow_options=None):
-        for name, v in (("h", h), ("w", w)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError("MatteScorer: %s must be an integer, got %r" % (name, v))
-            if v < 1:
-                raise ValueError("MatteScorer: %s must be at least 1, got %d" % (name, v))
+        self.h, self.w = ops.check_int("MatteScorer", "h", h, 1), ops.check_int("MatteScorer", "w", w, 1)
         if flow not in FLOW_MODES:
             raise ValueError("MatteScorer: flow must be one of %s, got %r" % (list(FLOW_MODES), flow))
         if flow_options is not None and flow != "estimate":
             raise ValueError("MatteScorer: flow_options go with flow='estimate'")
-        self.h, self.w, self.flow = int(h), int(w), flow
+        self.flow = flow
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("MatteScorer: a ROCm device is required, got %r" % (device,))
         self.flow_options = None
         if flow == "estimate":
-            opts = dict(ops.FLOW_DEFAULTS)
-            for k, v in dict(flow_options or {}).items():
-                if k not in opts:
-                    raise ValueError("MatteScorer: flow_options takes %s, got %r" % (sorted(opts), k))
-                opts[k] = v
-            self.flow_options = dict(zip(("levels", "warps", "iters", "alpha"),
-                                         ops.check_flow_options("MatteScorer", self.h, self.w, **opts)))
+            self.flow_options = ops.flow_options("MatteScorer: flow_options", self.h, self.w, flow_options)
         self._work = self._pyr = self._flow_work = None
         self.reset()
 

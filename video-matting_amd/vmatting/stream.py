@@ -39,7 +39,6 @@ from .split6 import rerun_x6
 
 PROPAGATE = "propagate"
 AUTO = "auto"
-FLOW_MODES = ("given", "estimate")
 
 
 class _Slot(Slot):
@@ -137,12 +136,14 @@ class FrameStream(SlotPipeline):
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
                              (h, w, chunk, depth))
         check_out("FrameStream", out)
+        # scale: the model's size and the guided filter's options
         self.scale = ops.check_scale("FrameStream", scale, smallest=1)
         if guided_options is not None and self.scale == 1:
             raise ValueError("FrameStream: guided_options go with scale > 1")
         if self.scale > 1:
-            self.guided = ops.guided_options("FrameStream", guided_options)
+            self.guided = ops.guided_options("FrameStream: guided_options", guided_options)
             self.hm, self.wm = ops.reduced_size(h, w, self.scale)
+        # trimap: one per frame, propagated from keys, made from the plate, or none
         if isinstance(trimap, str) and trimap not in (PROPAGATE, AUTO):
             raise ValueError("FrameStream: trimap must be True, False, %r or %r, got %r" % (PROPAGATE, AUTO, trimap))
         self.propagate = isinstance(trimap, str) and trimap == PROPAGATE
@@ -151,35 +152,27 @@ class FrameStream(SlotPipeline):
             raise ValueError("FrameStream: %s takes %d channels, so trimap must be %s" %
                              (type(model).__name__, model.IN_CH,
                               "True, %r or %r" % (PROPAGATE, AUTO) if model.IN_CH == 7 else False))
+        # trimap="auto": the plate trimap's options and the hole filling
         if auto_options is not None and not self.auto:
             raise ValueError("FrameStream: auto_options go with trimap=%r" % AUTO)
         if self.auto:
-            opts = dict(ops.PLATE_DEFAULTS)
-            for k, v in dict(auto_options or {}).items():
-                if k not in opts:
-                    raise ValueError("FrameStream: auto_options takes %s, got %r" % (sorted(opts), k))
-                opts[k] = v
-            self.auto_options = dict(zip(("lo", "hi", "r_bg", "r_fg"), ops.check_plate_options("FrameStream", **opts)))
+            self.auto_options = ops.plate_options("FrameStream: auto_options", auto_options)
         if auto_fill is not None and not self.auto:
             raise ValueError("FrameStream: auto_fill goes with trimap=%r" % AUTO)
         self.auto_fill = ops.check_fill("FrameStream: auto_fill", auto_fill)
+        # trimap="propagate": the unknown band's growth, and where the flows come from
         if not self.propagate and (flow is not None or flow_options is not None):
             raise ValueError("FrameStream: flow and flow_options go with trimap=%r" % PROPAGATE)
         self.grow = ops.check_grow("FrameStream", grow)
         flow = "estimate" if flow is None else flow
-        if flow not in FLOW_MODES:
-            raise ValueError("FrameStream: flow must be one of %s, got %r" % (FLOW_MODES, flow))
+        if flow not in ops.FLOW_MODES:
+            raise ValueError("FrameStream: flow must be one of %s, got %r" % (ops.FLOW_MODES, flow))
         self.estimate = self.propagate and flow == "estimate"
         if flow_options is not None and not self.estimate:
             raise ValueError("FrameStream: flow_options go with flow='estimate'")
         if self.estimate:
-            opts = dict(ops.FLOW_DEFAULTS)
-            for k, v in dict(flow_options or {}).items():
-                if k not in opts:
-                    raise ValueError("FrameStream: flow_options takes %s, got %r" % (sorted(opts), k))
-                opts[k] = v
-            self.flow_options = dict(zip(("levels", "warps", "iters", "alpha"),
-                                         ops.check_flow_options("FrameStream", h, w, **opts)))
+            self.flow_options = ops.flow_options("FrameStream: flow_options", h, w, flow_options)
+        # the plates
         static_bg = check_static_bg("FrameStream", static_bg, h, w)
         self.new_bg = check_new_bg("FrameStream", out, new_bg, h, w)
         self.model, self.h, self.w, self.chunk, self.depth = model, h, w, chunk, depth
@@ -366,9 +359,9 @@ class FrameStream(SlotPipeline):
         nw = self._new_plate if self._new_plate is not None else None if s.d_nw is None else s.d_nw[:k]
         s.download(s.alpha[:k], s.d_cmp[:k], bg, nw)
 
-    def _chain(self, s, k, keyed=False):
-        """Ingest -> forward -> quantise | compose -> download of the slot's first k frames, on the current stream;
-        with trimap="propagate" or "auto" the frames' trimaps first."""
+    def _before(self, s, k, keyed):
+        """What the chain of the slot's first k frames runs before the forward, on the current stream: with
+        trimap="propagate" or "auto" the frames' trimaps, then the ingest."""
         bg = self._plate if self._plate is not None else s.d_bg[:k]
         if self.propagate:
             self._trimaps(s, k, keyed)
@@ -377,36 +370,30 @@ class FrameStream(SlotPipeline):
             if self.auto_fill is not None:
                 ops.trimap_fill_enclosed(s.d_tri[:k], self.auto_fill, out=s.d_tri[:k], work=self._fill_work)
         self._feed(s, k, bg)
-        self.model.forward(s.frames[:k], out=self._matte(s, k), overflow=s.flag)
+
+    def _after(self, s, k):
+        """... and after it: the matte to full resolution (scale > 1), then quantise | compose -> download."""
         self._upsample(s, k)
         self._download(s, k)
 
-    def _capture(self, s, keyed=None):
+    def _chain(self, s, k, keyed=False):
+        """Ingest -> forward -> quantise | compose -> download of the slot's first k frames, on the current stream."""
+        self._before(s, k, keyed)
+        self.model.forward(s.frames[:k], out=self._matte(s, k), overflow=s.flag)
+        self._after(s, k)
+
+    def _capture(self, s, keyed=False):
         """The full-chunk chain of one slot as one HIP graph: UNet.capture records the forward over the slot's static
-        buffers with the ingest before it and the quantisation and download after it, all on the capturing stream.
-        ``keyed`` (trimap="propagate"): the graph of an item with a key, or of one that continues; the trimap chain
-        heads it."""
-        bg = self._plate if self._plate is not None else s.d_bg
-
-        def pre():
-            if keyed is not None:
-                self._trimaps(s, self.chunk, keyed)
-            if self.auto:
-                ops.trimap_from_plate(s.d_cmp, bg, out=s.d_tri, work=self._auto_work, **self.auto_options)
-                if self.auto_fill is not None:
-                    ops.trimap_fill_enclosed(s.d_tri, self.auto_fill, out=s.d_tri, work=self._fill_work)
-            self._feed(s, self.chunk, bg)
-
-        def post():
-            self._upsample(s, self.chunk)
-            self._download(s, self.chunk)
-
-        graph = self.model.capture(s.frames, static=True, out=self._matte(s, self.chunk), overflow=s.flag, pre=pre,
-                                   post=post)
-        if keyed is None:
-            s.graph = graph
-        else:
+        buffers with _before ahead of it and _after behind it, all on the capturing stream; a leading slice of full
+        length is the buffer itself, so these are _chain's calls.  ``keyed`` (trimap="propagate"): the graph of an item
+        with a key, or of one that continues."""
+        n = self.chunk
+        graph = self.model.capture(s.frames, static=True, out=self._matte(s, n), overflow=s.flag,
+                                   pre=lambda: self._before(s, n, keyed), post=lambda: self._after(s, n))
+        if self.propagate:
             s.graphs[keyed] = graph
+        else:
+            s.graph = graph
 
     def _submit(self, s, index, cmp, bg, tri, k, nw=None, bw=None):
         s.k, s.index = k, index
@@ -438,8 +425,7 @@ class FrameStream(SlotPipeline):
             with torch.cuda.stream(self._compute):
                 rerun_x6(self, s.frames[:k], self._matte(s, k))
                 s.flag.zero_()
-                self._upsample(s, k)
-                self._download(s, k)
+                self._after(s, k)
             self._compute.synchronize()
         return s.h_out[:k].numpy().copy()
 
