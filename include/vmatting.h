@@ -748,7 +748,7 @@ int vm_trimap_propagate(const uint8_t* prev, const float* flow, int h, int w, in
  *   out   uint8 [n,h,w]: 255 where F, 0 where B, 128 elsewhere (lo < hi: the two exclude each other); it must not
  *         overlap cmp or bg
  * What this is not: it has no shadow or exposure model (a shadow on the plate or a gain change is a difference like
- * any other).  It cannot tell a translucent high-contrast pixel from an opaque one, so r_fg must exceed the width of
+ * any other; vm_plate_gain_fit / vm_plate_gain_apply below match the plate's exposure to the frame before this call).  It cannot tell a translucent high-contrast pixel from an opaque one, so r_fg must exceed the width of
  * the soft edge.  Foreground that matches the plate over an area wider than 2 r_bg + 1 is labelled background.
  * tests/trimap_plate_ref.py restates the definition in numpy; the kernels match it byte for byte.
  * Two launches for all n frames (csrc/trimap_plate.hip): the candidates B0 and F0 as bit rows into `work` (0.25 B per
@@ -813,7 +813,8 @@ int vm_trimap_fill_enclosed(const uint8_t* trimap, int n, int h, int w, int max_
  * Consequences: a pixel that the subject covers in at most (n - 1) / 2 samples and that shows one value in all others
  * gets that value, whatever covered it; covered in at most (n - 1) / 4 samples, its spread is 0 as well.
  * What this is not: it needs a locked-off camera; a pixel covered in more than half the samples gets the subject's
- * colour (spread shows it); there is no exposure or flicker compensation.
+ * colour (spread shows it); there is no exposure or flicker compensation (vm_plate_gain_fit matches a finished plate
+ * to a frame; the samples themselves are taken as they are).
  * tests/plate_ref.py restates the definition in numpy; the kernel matches it byte for byte.
  * One launch (csrc/plate.hip): a thread per dword of the frame, the n samples of its 4 bytes in registers through a
  * sorting network.  samples, plate and spread may sit at any byte address.  No byte outside plate[0 : h*w*3] and
@@ -931,6 +932,43 @@ size_t vm_guided_workspace_bytes(int n, int hm, int wm);
 int vm_guided_coeffs(const uint8_t* guide, const float* p, int n, int hm, int wm, int r, double eps, float* ab,
                      void* work, void* stream);
 int vm_guided_apply(const float* ab, const uint8_t* cmp, int n, int h, int w, int scale, float* alpha, void* stream);
+
+/* ---------------------------------------------------------------- the plate's exposure matched to the frame
+ * Everything driven by the background (the model's input, the plate trimap, the compose modes) takes the plate and the
+ * frame to be shot at one exposure; auto-exposure, lamp flicker or a plate shot earlier shift the whole frame by 10 - 25 %.
+ * One gain per frame and colour channel is fitted between frame and plate and the plate is scaled by it (the reference
+ * has no counterpart: its backgrounds are the composites' own).  All integer.  Per frame i and channel c, with
+ * a = cmp[i,y,x,c] and b = bg[i or 0,y,x,c]:
+ *   cmp      uint8 [n,h,w,3] BGR; bg uint8 [nb,h,w,3], nb == n or nb == 1 (one static plate), as vm_frames_from_u8
+ *   valid    16 <= b <= 250, a <= 250 and t = 64 a + (b >> 1) < 255 b: a dark plate byte carries no ratio, a clipped byte
+ *            a false one, and the last condition keeps the clamp bin 255 out of the histogram
+ *   bin      q = t / b (integer division), 0..254: the ratio a / b to the nearest 1/64
+ *   H, S     H[q] counts the valid pixels; S[q] = H[q - 1] + H[q] + H[q + 1], H[-1] = H[255] = 0
+ *   mode     q0 = the smallest q in 16..254 at which S is largest (no valid pixel: 16).  The mode and not a least-squares
+ *            fit over everything: the subject's pixels are outliers of any size
+ *   inlier   valid and |64 a - q0 b| <= band b;  band 1..16
+ *   sums     over the inliers, int64: cnt, N = sum a b, D = sum b b
+ *   gain     int32 [n,3], Q12: G = (4096 N + (D >> 1)) / D if cnt * min_share >= h w, else 4096 (the identity);
+ *            min_share 1..4096.  G lies within 64 (q0 -+ band), so G <= 17281
+ *   support  int32 [n,3]: cnt in both cases; a small support says the fit is not to be trusted
+ *   apply    out uint8 [n,h,w,3]: out = min(255, (G[i,c] b + 2048) >> 12).  Gains outside 0 .. 2^20 are taken as the nearer
+ *            end (for G >= 0 that changes no result and G b stays within 32 bits)
+ * What this is not: one multiplicative gain per channel and frame - no offset, no shadows, no vignetting or local change;
+ * a clipped region gets no match; the fit fails where the subject and not the background is the largest population of
+ * one ratio, or where too little of the plate lies within 16..250 (support shows it; below h w / min_share the gain is the
+ * identity).  tests/plate_gain_ref.py restates the definition in numpy; the kernels match it exactly.
+ * vm_plate_gain_fit is four launches for all n frames (csrc/plate_gain.hip): it zeroes the part of `work` it uses, adds
+ * per-block LDS histograms into it, finds each frame's modes and adds the inlier sums, and finishes the quotients;
+ * integer atomics only, so the result does not depend on their order.  vm_plate_gain_apply is one launch.
+ *   work     vm_plate_gain_workspace_bytes(n) bytes, 16-byte aligned; the call initialises what it reads of it
+ * cmp, bg and out may sit at any byte address; gain and support are 4-byte aligned.  No allocation, no synchronisation
+ * and no host read-back inside: the calls can be captured in a graph.  VM_EINVAL for a NULL pointer, n, h or w < 1,
+ * n * h * w * 3 beyond 2^31 - 1, nb not 1 or n, band or min_share out of range, out overlapping bg or gain, or a misaligned
+ * gain / support / work (checked before any HIP call); the size query returns 0 for n < 1. */
+size_t vm_plate_gain_workspace_bytes(int n);
+int vm_plate_gain_fit(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int h, int w, int band, int min_share,
+                      int32_t* gain, int32_t* support, void* work, void* stream);
+int vm_plate_gain_apply(const uint8_t* bg, int nb, const int32_t* gain, int n, int h, int w, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }

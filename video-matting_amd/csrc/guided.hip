@@ -21,21 +21,6 @@ namespace {
 
 constexpr int SCALE_MIN = 2, SCALE_MAX = 4;
 
-// dst[i] = the 4 bytes at p + 4 i, i < ND, from the aligned dwords around them (v_alignbyte_b32 shifts a pair right by
-// k = 0..3 bytes)
-template <int ND>
-__device__ __forceinline__ void load_bytes(const uint8_t* __restrict__ p, uint32_t* dst) {
-  const uint32_t k = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3);
-  const uint32_t* q = reinterpret_cast<const uint32_t*>(p - k);
-  uint32_t d[ND + 1];
-#pragma unroll
-  for (int i = 0; i < ND; ++i) d[i] = q[i];
-  d[ND] = k ? q[ND] : 0u;
-#pragma unroll
-  for (int i = 0; i < ND; ++i) dst[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], k);
-}
-__device__ __forceinline__ uint32_t byte_of(const uint32_t* d, int i) { return (d[i >> 2] >> (8 * (i & 3))) & 255u; }
-
 // ---------------------------------------------------------------- vm_frames_reduce_u8
 // One thread makes P consecutive output pixels of one output row: P C = 12 (BGR) or 16 (trimap) bytes, stored as dwords
 // when the output address allows it.  Where its P blocks are whole in x it reads each of the block's rows as P S C / 4

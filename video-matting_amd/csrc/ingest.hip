@@ -62,7 +62,6 @@ __device__ __forceinline__ void load12(const uint8_t* p, long off, uint32_t* w) 
   const uint32_t* q = reinterpret_cast<const uint32_t*>(p + off);
   w[0] = q[0]; w[1] = q[1]; w[2] = q[2];
 }
-__device__ __forceinline__ uint32_t byte_of(const uint32_t* w, int i) { return (w[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
 
 // DENSE = 1: f32 [pixels, C] without gaps, 16-byte aligned -> 4 pixels are C float4 stores; BF8 = 1: 4 uint4 stores.
 // DENSE = 0 and BF8 = 0: f32 at a channel offset / stride, one pixel per thread and scalar stores.

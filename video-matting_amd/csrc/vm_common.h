@@ -145,6 +145,22 @@ struct Chunk<uint16_t> {
   }
 };
 
+// Byte rows at any address read with whole dwords: dst[i] = the 4 bytes at p + 4 i, i < ND, from the aligned dwords
+// around them (v_alignbyte_b32 shifts a pair right by k = 0..3 bytes).  Every dword read holds at least one byte of
+// the span, and an aligned dword never straddles a page.
+template <int ND>
+__device__ __forceinline__ void load_bytes(const uint8_t* __restrict__ p, uint32_t* dst) {
+  const uint32_t k = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3);
+  const uint32_t* q = reinterpret_cast<const uint32_t*>(p - k);
+  uint32_t d[ND + 1];
+#pragma unroll
+  for (int i = 0; i < ND; ++i) d[i] = q[i];
+  d[ND] = k ? q[ND] : 0u;
+#pragma unroll
+  for (int i = 0; i < ND; ++i) dst[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], k);
+}
+__device__ __forceinline__ uint32_t byte_of(const uint32_t* d, int i) { return (d[i >> 2] >> (8 * (i & 3))) & 255u; }
+
 // Decoded uint8 BGR -> the network's feed (loader.py:45,75-78): the mean is subtracted in float64 and the result is
 // rounded to f32 once.  One subtraction, no multiply-add pair: -ffp-contract does not change it.
 __device__ __forceinline__ double vgg_mean_d(int c) { return c == 0 ? 103.939 : c == 1 ? 116.779 : 123.68; }

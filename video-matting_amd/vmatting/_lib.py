@@ -219,6 +219,10 @@ SIGNATURES = [
     ("vm_guided_coeffs", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p,
                           c_void_p]),
     ("vm_guided_apply", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("vm_plate_gain_workspace_bytes", c_size_t, [c_int]),
+    ("vm_plate_gain_fit", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
+    ("vm_plate_gain_apply", c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
 ]
 
 _lib = None

@@ -8,7 +8,15 @@ warm-up allocated
 belongs to the side stream as far as the caching allocator knows, while the graphs replay on the caller's stream:
 ``record_stream`` tells it, so that a buffer set freed later (the model moved to another shape and the graph was
 dropped) is not handed out again while replays queued on the caller's stream may still use it.
+
+No garbage collection may run while a capture is under way: on ROCm a torch.cuda.CUDAGraph synchronises the device when
+it is destroyed, a capture under way refuses that call, and the error, raised in a destructor, ends the process.  A dead
+reference cycle that holds an earlier graph (a stream whose source raised keeps one alive through the exception's
+traceback) is collected whenever the collector next runs, and torch no longer collects on entering a capture.  So
+capture_passes collects before it records and keeps the collector off until the last pass is recorded.
 """
+
+import gc
 
 import torch
 
@@ -56,11 +64,18 @@ def capture_passes(device, passes, keep=None, hook=None):
     for t in _tensors([list(keep()) if keep is not None else (), list(ops._ws_cache.values())]):
         t.record_stream(main)
     graphs, results = [], []
-    for p in passes:
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            if hook is not None:
-                hook()
-            results.append(p())
-        graphs.append(g)
+    gc.collect()
+    collecting = gc.isenabled()
+    gc.disable()
+    try:
+        for p in passes:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                if hook is not None:
+                    hook()
+                results.append(p())
+            graphs.append(g)
+    finally:
+        if collecting:
+            gc.enable()
     return graphs, results

@@ -1520,6 +1520,82 @@ def guided_upsample(alpha_lo, guide_hi, scale, r=GUIDED_DEFAULTS["r"], eps=GUIDE
     return guided_apply(guided_coeffs(guide_lo, alpha_lo, r, eps), guide_hi, scale)
 
 
+# ---------------------------------------------------------------- the plate's exposure matched to the frame
+
+# the inlier band around the mode in 1/64 of the ratio, and the share of the frame (1 / min_share) the inliers must
+# reach; band 8 from the CPU prototype (4 was worse by half), untuned on real footage
+GAIN_DEFAULTS = {"band": 8, "min_share": 16}
+GAIN_BAND_MAX, GAIN_SHARE_MAX = 16, 4096
+GAIN_ONE = 4096  # the gains are Q12 integers
+
+
+def check_gain_options(who, band=GAIN_DEFAULTS["band"], min_share=GAIN_DEFAULTS["min_share"]):
+    """The options of vm_plate_gain_fit as it checks them, on the host: integers, band in 1..16 and min_share in
+    1..4096 -> (band, min_share)."""
+    return check_int(who, "band", band, 1, GAIN_BAND_MAX), check_int(who, "min_share", min_share, 1, GAIN_SHARE_MAX)
+
+
+def gain_options(who, options):
+    """A dict over GAIN_DEFAULTS (None: the defaults), checked -> {"band": band, "min_share": min_share}."""
+    return _options(who, GAIN_DEFAULTS, options, check_gain_options)
+
+
+GAIN_FIT = "fit"
+
+
+def check_gain_mode(who, gain, options):
+    """The ``gain`` argument of FrameStream and reader.trimap_from_plate: None or "fit", and their ``gain_options`` (a
+    dict over GAIN_DEFAULTS) only with "fit" -> the checked options, or None without a gain."""
+    if gain is not None and not (isinstance(gain, str) and gain == GAIN_FIT):
+        raise ValueError("%s: gain must be None or %r, got %r" % (who, GAIN_FIT, gain))
+    if gain is None:
+        if options is not None:
+            raise ValueError("%s: gain_options go with gain=%r" % (who, GAIN_FIT))
+        return None
+    return gain_options("%s: gain_options" % who, options)
+
+
+def plate_gain_workspace_bytes(n):
+    return lib().vm_plate_gain_workspace_bytes(n)
+
+
+def plate_gain_fit(cmp, bg, band=GAIN_DEFAULTS["band"], min_share=GAIN_DEFAULTS["min_share"], out=None, support=None,
+                   work=None):
+    """vm_plate_gain_fit: one gain per frame and colour channel between the frames and their background.  cmp u8
+    [n,h,w,3] BGR, bg u8 [n,h,w,3] or one static plate [h,w,3] / [1,h,w,3] -> (gain, support), both int32 [n,3]: the
+    gain in Q12 (4096 is 1.0) is the least-squares ratio over the pixels within ``band`` / 64 of the histogram mode of
+    cmp / bg, or 4096 where fewer than h w / ``min_share`` pixels are; support is their count (include/vmatting.h).
+    ``out`` / ``support``: contiguous int32 [n,3] device tensors; ``work``: a uint8 device buffer of
+    plate_gain_workspace_bytes(n); all allocated when None."""
+    who = "plate_gain_fit"
+    n, h, w, nb = _check_frames_and_bg(who, cmp, bg)
+    band, min_share = check_gain_options(who, band, min_share)
+    out = _out_or_new(who, "out", out, torch.int32, "n,3", cmp.device, ValueError, n=n)
+    support = _out_or_new(who, "support", support, torch.int32, "n,3", cmp.device, ValueError, n=n)
+    for t in (cmp, bg, out, support):
+        _require_gpu(t)
+    work = _buffer_or_new(who, "work", work, torch.uint8, plate_gain_workspace_bytes(n), cmp.device)
+    check(lib().vm_plate_gain_fit(_ptr(cmp), _ptr(bg), nb, n, h, w, band, min_share, _ptr(out), _ptr(support),
+                                  _ptr(work), stream_handle()), who)
+    return out, support
+
+
+def plate_gain_apply(bg, gain, out=None):
+    """vm_plate_gain_apply: the plate under the gains.  bg u8 [n,h,w,3], or one static plate [h,w,3] / [1,h,w,3] for
+    all n rows of ``gain`` (int32 [n,3], Q12, as plate_gain_fit returns it) -> u8 [n,h,w,3] = min(255, (gain * bg +
+    2048) >> 12) (include/vmatting.h).  ``out``: a contiguous uint8 [n,h,w,3] device tensor, allocated when None."""
+    who = "plate_gain_apply"
+    n, _ = _check_tensor(who, "gain", gain, (torch.int32,), "n,3")
+    shape = _check_tensor(who, "bg", bg, (torch.uint8,), "n,h,w,3 | 1,h,w,3 | h,w,3", n=n)
+    h, w = shape[-3], shape[-2]
+    nb = n if shape == (n, h, w, 3) else 1
+    out = _out_or_new(who, "out", out, torch.uint8, "n,h,w,3", bg.device, ValueError, n=n, h=h, w=w)
+    for t in (bg, gain, out):
+        _require_gpu(t)
+    check(lib().vm_plate_gain_apply(_ptr(bg), nb, _ptr(gain), n, h, w, _ptr(out), stream_handle()), who)
+    return out
+
+
 # ---------------------------------------------------------------- training step (train.py:288-343, config 5)
 
 def matting_loss_backward(pred, gt, raw_fg, in_bg, in_cmp, out=None):

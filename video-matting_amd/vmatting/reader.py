@@ -173,18 +173,47 @@ def fill_enclosed(trimap_u8, max_area=0):
     return out[0] if single else out
 
 
-def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, fill=None):
+def match_plate(cmp_u8, bg_u8, **options):
+    """The background plate brought to one frame's exposure: what FrameStream(gain="fit") puts in the plate's place.
+    cmp_u8, bg_u8 uint8 [h,w,3] BGR; ``options`` over ops.GAIN_DEFAULTS (band, min_share) -> (plate uint8 [h,w,3], gains
+    f32 [3], support int [3]): per channel one gain, the least-squares ratio frame / plate over the pixels near the mode
+    of that ratio's histogram, and the plate times it, clamped at 255 (ops.plate_gain_fit, ops.plate_gain_apply,
+    include/vmatting.h).  ``support`` counts the pixels the fit rests on; below h w / min_share the gain is 1.  No offset,
+    no shadows, nothing local.  numpy in, numpy out, through the kernels."""
+    from vmatting import ops
+    who = "match_plate"
+    opts = ops.gain_options(who, options)
+    cmp_u8, bg_u8 = np.asarray(cmp_u8), np.asarray(bg_u8)
+    for name, a in (("cmp", cmp_u8), ("bg", bg_u8)):
+        if a.dtype != np.uint8:
+            raise TypeError("%s: %s must be uint8, got %s" % (who, name, a.dtype))
+    if cmp_u8.ndim != 3 or cmp_u8.shape[2] != 3 or cmp_u8.size == 0:
+        raise ValueError("%s: cmp must be [h,w,3] BGR, got %s" % (who, cmp_u8.shape))
+    if bg_u8.shape != cmp_u8.shape:
+        raise ValueError("%s: bg must be [h,w,3] like cmp %s, got %s" % (who, cmp_u8.shape, bg_u8.shape))
+    cmp, bg = (torch.from_numpy(np.ascontiguousarray(a)[None]).cuda() for a in (cmp_u8, bg_u8))
+    gain, support = ops.plate_gain_fit(cmp, bg, **opts)
+    plate = ops.plate_gain_apply(bg, gain)
+    return (plate[0].cpu().numpy(), gain[0].cpu().numpy().astype(np.float32) / np.float32(ops.GAIN_ONE),
+            support[0].cpu().numpy().astype(np.int64))
+
+
+def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, fill=None, gain=None,
+                      gain_options=None):
     """The trimap of a frame from its difference to the background plate: what FrameStream(trimap="auto") feeds the
     model, and the trimap of a clip's first frame for ClipStream's alpha0.  cmp_u8 uint8 BGR, one frame [H,W,3] or a
     stack [N,H,W,3]; bg_u8 uint8 [H,W,3] (one plate) or, with a stack, [N,H,W,3] -> uint8 [H,W] or [N,H,W]: 0 where the
     frame equals the plate within ``lo`` levels over a (2 r_bg + 1)^2 window, 255 where it differs by ``hi`` or more
     over a (2 r_fg + 1)^2 window, 128 elsewhere (ops.trimap_from_plate, include/vmatting.h; None: ops.PLATE_DEFAULTS,
-    which are untuned).  No shadow or exposure model.  ``fill`` (FrameStream's ``auto_fill``): True, or an integer area
-    cap, turns the enclosed background of the result unknown (fill_enclosed); None or False leaves it.  numpy arrays
-    return numpy, device tensors stay on the device."""
+    which are untuned).  No shadow model, and no exposure model unless ``gain`` is "fit" (FrameStream's ``gain``): every
+    frame is then compared with the plate under that frame's fitted gains (match_plate; ``gain_options`` over
+    ops.GAIN_DEFAULTS).  ``fill`` (FrameStream's ``auto_fill``): True, or an integer area cap, turns the enclosed
+    background of the result unknown (fill_enclosed); None or False leaves it.  numpy arrays return numpy, device tensors
+    stay on the device."""
     from vmatting import ops
     who = "trimap_from_plate"
     cap = ops.check_fill(who, fill)
+    gopts = ops.check_gain_mode(who, gain, gain_options)
     if isinstance(cmp_u8, torch.Tensor) != isinstance(bg_u8, torch.Tensor):
         raise TypeError("%s: cmp and bg are both numpy arrays or both torch tensors" % who)
     given = {"lo": lo, "hi": hi, "r_bg": r_bg, "r_fg": r_fg}
@@ -198,9 +227,12 @@ def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, 
         raise ValueError("%s: one [H,W,3] frame takes one [H,W,3] plate, got %s" % (who, tuple(bg_u8.shape)))
     ops._check_u8_frames(cmp, bg_u8, None)
     if device:
-        out = ops.trimap_from_plate(cmp.contiguous(), bg_u8.contiguous(), **opts)
+        cmp, bg = cmp.contiguous(), bg_u8.contiguous()
     else:
-        out = ops.trimap_from_plate(torch.from_numpy(cmp).cuda(), torch.from_numpy(bg_u8).cuda(), **opts)
+        cmp, bg = torch.from_numpy(cmp).cuda(), torch.from_numpy(bg_u8).cuda()
+    if gopts is not None:
+        bg = ops.plate_gain_apply(bg, ops.plate_gain_fit(cmp, bg, **gopts)[0])
+    out = ops.trimap_from_plate(cmp, bg, **opts)
     if cap is not None:
         ops.trimap_fill_enclosed(out, cap, out=out)
     if not device:

@@ -21,6 +21,10 @@ the frames only, never on the model's output, so the forward stays chunked.
 ``trimap="auto"``: the user has no trimap at all.  The chunk's chain starts with ops.trimap_from_plate on the uploaded
 frames and the plate, followed with ``auto_fill`` by ops.trimap_fill_enclosed in place; nothing is kept between chunks.
 
+``gain="fit"``: the plate and the frames were not shot at one exposure.  The chunk's chain starts with
+ops.plate_gain_fit and ops.plate_gain_apply: one gain per frame and colour channel, and a gained copy of the plate per
+frame, which everything after it in the chain takes for the background.
+
 ``scale=2..4``: the frames are larger than the model should see (2160 x 3840).  The chunk's chain reduces the uploaded
 frames (and per-frame backgrounds and trimaps) by ``scale`` (ops.frames_reduce_u8), runs the model on the reduced
 frames, and carries its matte back to the frames' size with a guided filter steered by the full-resolution frame
@@ -60,13 +64,18 @@ class _Slot(Slot):
             self.d_tri = torch.zeros((n, h, w), dtype=u8, device=fs.device)
             if fs.estimate:
                 self.d_bw = torch.zeros((n, h, w, 2), dtype=torch.float32, device=fs.device)
+        if fs.gain is not None:  # the chunk's background under its frames' gains, the gains and their support
+            self.g_bg = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device)
+            self.gain = torch.zeros((n, 3), dtype=torch.int32, device=fs.device)
+            self.support = torch.zeros((n, 3), dtype=torch.int32, device=fs.device)
         self.graphs = {}  # trimap="propagate": the full-chunk graph of a keyed item (True) and of a continued one
         if fs.scale > 1:
             # the model's side of the chunk: the reduced uint8 frames it is fed from, its matte, and the guided
             # filter's coefficients; the frame buffer below is then the model's size too
             h, w = fs.hm, fs.wm
             self.r_cmp = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device)
-            self.r_bg = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device) if fs.static_bg is None else None
+            per_frame = fs.static_bg is None or fs.gain is not None
+            self.r_bg = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device) if per_frame else None
             self.r_tri = torch.zeros((n, h, w), dtype=u8, device=fs.device) if fs.trimap else None
             self.alpha_lo = torch.empty((n, h, w, 1), dtype=torch.float32, device=fs.device)
             self.ab = torch.empty((n, h, w, 4), dtype=torch.float32, device=fs.device)
@@ -126,11 +135,25 @@ class FrameStream(SlotPipeline):
     ops.GUIDED_DEFAULTS (r, eps; untuned on real footage), only with scale > 1.  Every ``out`` mode works on the
     full-resolution matte.  scale=1 is the stream without any of this, call for call.
 
+    ``gain`` (None, the default, or "fit"): match the background's exposure to every frame before anything uses it.
+    Per frame and colour channel one multiplicative gain is fitted between the frame and the background (the static
+    plate, or the item's per-frame ``bg``) on the device (ops.plate_gain_fit, ``gain_options`` a dict over
+    ops.GAIN_DEFAULTS: band, min_share; untuned on real footage), and a copy of the background under those gains
+    (ops.plate_gain_apply) stands in for it in the rest of the chain: the automatic trimap, the model's feed (with
+    ``scale`` its reduction) and the compose modes.  The mattes are those of a stream fed these gained backgrounds as
+    per-frame ``bg``, bit for bit; reader.match_plate shows one.  ``last_gains()`` returns the last chunk's gains and
+    their support after a run.  What it is not: one gain per channel and frame, so no offset, no shadows, no
+    vignetting or local change; a clipped region gets no match; the fit fails where the subject and not the background
+    is the largest population of one ratio, or where too little of the plate lies within 16..250 - ``support`` shows
+    it, and below h w / min_share the gain is 1; the new plate of out="over" is not gained.  gain=None is the stream
+    without any of this, call for call.  ClipStream, VideoMatter and PlateEstimator do not take it.
+
     If the source raises, or yields a wrong shape, dtype or k, the chunks already taken are finished and yielded, the
     streams are synchronised, and the exception then propagates; the object can run again."""
 
     def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True, new_bg=None,
-                 flow=None, flow_options=None, grow=1, auto_options=None, auto_fill=None, scale=1, guided_options=None):
+                 flow=None, flow_options=None, grow=1, auto_options=None, auto_fill=None, scale=1, guided_options=None,
+                 gain=None, gain_options=None):
         h, w, chunk, depth = int(h), int(w), int(chunk), int(depth)
         if h < 1 or w < 1 or chunk < 1 or depth < 1:
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
@@ -172,6 +195,8 @@ class FrameStream(SlotPipeline):
             raise ValueError("FrameStream: flow_options go with flow='estimate'")
         if self.estimate:
             self.flow_options = ops.flow_options("FrameStream: flow_options", h, w, flow_options)
+        # gain="fit": the fit's options (None: no gain)
+        self.gain = ops.check_gain_mode("FrameStream", gain, gain_options)
         # the plates
         static_bg = check_static_bg("FrameStream", static_bg, h, w)
         self.new_bg = check_new_bg("FrameStream", out, new_bg, h, w)
@@ -181,6 +206,7 @@ class FrameStream(SlotPipeline):
         self.overflowed_chunks = []
         self._plate = self._new_plate = None
         self._plate_lo = self._guided_work = None  # scale > 1: the reduced plate, the guided filter's workspace
+        self._gain_work = self._gain_last = None   # gain="fit": the fit's workspace; the last chunk's (slot, frames)
         self._x6 = None
         self._keyed = False      # trimap="propagate": whether this run has had its first key
         self._tri_last = None    # ... and the last frame's trimap, at a fixed device address
@@ -260,12 +286,15 @@ class FrameStream(SlotPipeline):
         if self.static_bg is not None:
             self._plate = torch.from_numpy(self.static_bg).to(self.device)
         if self.scale > 1:  # the plate at the model's size, once; one workspace for every slot, like _auto_work
-            if self._plate is not None:
+            if self._plate is not None and self.gain is None:  # (a gained plate is reduced per chunk)
                 self._plate_lo = ops.frames_reduce_u8(self._plate[None], self.scale)
             self._guided_work = torch.zeros(ops.guided_workspace_bytes(self.chunk, self.hm, self.wm), dtype=torch.uint8,
                                             device=self.device)
         if isinstance(self.new_bg, np.ndarray):
             self._new_plate = torch.from_numpy(self.new_bg).to(self.device)
+        if self.gain is not None:  # one workspace for every slot, like _auto_work
+            self._gain_work = torch.zeros(ops.plate_gain_workspace_bytes(self.chunk), dtype=torch.uint8,
+                                          device=self.device)
         if self.propagate:
             self._setup_propagate()
         if self.auto:  # one workspace for every slot: the chains run one after another on the compute stream
@@ -327,6 +356,24 @@ class FrameStream(SlotPipeline):
             raise RuntimeError("FrameStream: last_trimap() before any frame was submitted")
         return self._tri_last.cpu().numpy()
 
+    def last_gains(self):
+        """gain="fit": (gains f32 [k,3] = Q12 gain / 4096, support int [k,3]) of the last chunk submitted, once the run
+        has drained."""
+        if self.gain is None:
+            raise ValueError("FrameStream: last_gains() goes with gain='fit'")
+        if self._gain_last is None:
+            raise RuntimeError("FrameStream: last_gains() before any frame was submitted")
+        s, k = self._gain_last
+        return (s.gain[:k].cpu().numpy().astype(np.float32) / np.float32(ops.GAIN_ONE),
+                s.support[:k].cpu().numpy().astype(np.int64))
+
+    def _background(self, s, k):
+        """What the chain of the slot's first k frames takes for the background: the plate, the uploaded per-frame
+        backgrounds, or with gain="fit" the slot's gained copy (made by _before)."""
+        if self.gain is not None:
+            return s.g_bg[:k]
+        return self._plate if self._plate is not None else s.d_bg[:k]
+
     def _feed(self, s, k, bg):
         """The network input of the slot's first k frames from its uint8 frames; with scale > 1 from their reductions."""
         tri = None if s.d_tri is None else s.d_tri[:k]
@@ -334,7 +381,7 @@ class FrameStream(SlotPipeline):
             ops.frames_from_u8(s.d_cmp[:k], bg, tri, out=s.frames[:k])
             return
         ops.frames_reduce_u8(s.d_cmp[:k], self.scale, out=s.r_cmp[:k])
-        if self._plate is None:
+        if self._plate_lo is None:
             bg = ops.frames_reduce_u8(bg, self.scale, out=s.r_bg[:k])
         else:
             bg = self._plate_lo
@@ -355,14 +402,19 @@ class FrameStream(SlotPipeline):
 
     def _download(self, s, k):
         """The result of the slot's first k frames from its alpha (and, composed, its uint8 inputs)."""
-        bg = self._plate if self._plate is not None else s.d_bg[:k]
+        bg = self._background(s, k)
         nw = self._new_plate if self._new_plate is not None else None if s.d_nw is None else s.d_nw[:k]
         s.download(s.alpha[:k], s.d_cmp[:k], bg, nw)
 
     def _before(self, s, k, keyed):
         """What the chain of the slot's first k frames runs before the forward, on the current stream: with
-        trimap="propagate" or "auto" the frames' trimaps, then the ingest."""
-        bg = self._plate if self._plate is not None else s.d_bg[:k]
+        gain="fit" the gains and the gained background, with trimap="propagate" or "auto" the frames' trimaps, then the
+        ingest."""
+        if self.gain is not None:
+            bg = self._plate if self._plate is not None else s.d_bg[:k]
+            ops.plate_gain_fit(s.d_cmp[:k], bg, out=s.gain[:k], support=s.support[:k], work=self._gain_work, **self.gain)
+            ops.plate_gain_apply(bg, s.gain[:k], out=s.g_bg[:k])
+        bg = self._background(s, k)
         if self.propagate:
             self._trimaps(s, k, keyed)
         if self.auto:
@@ -397,6 +449,8 @@ class FrameStream(SlotPipeline):
 
     def _submit(self, s, index, cmp, bg, tri, k, nw=None, bw=None):
         s.k, s.index = k, index
+        if self.gain is not None:
+            self._gain_last = (s, k)
         keyed = self.propagate and tri is not None
         for name, a in (("cmp", cmp), ("bg", bg), ("key" if self.propagate else "tri", tri), ("bw", bw), ("nw", nw)):
             s.stage(name, a, 1 if name == "key" else k)
