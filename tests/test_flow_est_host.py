@@ -181,3 +181,23 @@ def test_clip_stream_estimate_mode_checks_on_the_host():
     with pytest.raises(ValueError, match="cmp0"):
         first(given, (cmp, bg, bw, None), cmp0=cmp)
     assert given._slots is None
+
+
+def test_flow_tracker_rows_are_16_byte_aligned(monkeypatch):
+    """FlowTracker's buffers, allocated on the host here (nothing runs): frames + 1 rows of a multiple of 4 floats.
+    The library's count is one already at every size tried, so the round-up is shown on a count that needs it."""
+    from vmatting import ops
+    from vmatting.flow_track import FlowTracker
+    count = ops.flow_pyramid_floats
+    for h, w, levels, frames in ((24, 40, 6, 1), (70, 90, 6, 3), (133, 261, 2, 8)):
+        opts = ops.flow_options("t", h, w, {"levels": levels})
+        assert count(h, w, levels) % 4 == 0
+        for extra in (0, 1, 2, 3):
+            monkeypatch.setattr(ops, "flow_pyramid_floats", lambda *a, extra=extra: count(*a) + extra)
+            tr = FlowTracker(h, w, opts, "cpu", frames=frames)
+            monkeypatch.undo()
+            floats = count(h, w, levels) + (4 if extra else 0)
+            assert tr.rows.shape == (frames + 1, floats) and tr.rows.dtype == torch.float32 and not tr.rows.any()
+            assert all(tr.rows[j].data_ptr() % 16 == 0 for j in range(frames + 1))
+            assert tr.work.dtype == torch.uint8 and tr.work.numel() == ops.flow_workspace_bytes(h, w, levels)
+            assert tr.options == opts and tr.options is not opts

@@ -200,6 +200,38 @@ def test_estimator_uses_the_schedules_frames():
     assert np.array_equal(got[0], ref.plate(clip[sched.kept()])[0])
 
 
+def test_a_strided_device_clip_is_taken_as_it_is():
+    """reader.plate_from_clip and PlateEstimator.add copy the frames they keep one by one, so a device clip of any
+    strides is taken: every second frame, a window of every frame, and a clip stored [N,W,H,3] seen as [N,H,W,3] give
+    the plates of their contiguous copies."""
+    from vmatting import PlateEstimator, reader
+    clip = dev(ref.noise(21, 12, 10))
+    views = [clip[::2], clip[:, 1:11:2, 3:], clip.permute(0, 2, 1, 3)]
+    for view in views:
+        assert not view.is_contiguous()
+        host = view.cpu().numpy()
+        want = ref.plate(host[kept_frames(host.shape[0])])
+        plate, spread = reader.plate_from_clip(view, capacity=8)
+        assert plate.is_cuda and np.array_equal(plate.cpu().numpy(), want[0])
+        assert np.array_equal(spread.cpu().numpy(), want[1])
+        est = PlateEstimator(host.shape[1], host.shape[2], capacity=8)
+        for a in range(0, host.shape[0], 4):
+            est.add(view[a:a + 4])
+        est.add(view[0])                                      # and one frame on its own, strided too in two of the views
+        assert est.frames_seen == host.shape[0] + 1
+        assert np.array_equal(est.result()[0].cpu().numpy(),
+                              ref.plate(np.concatenate([host, host[:1]])[kept_frames(host.shape[0] + 1)])[0])
+
+
+def kept_frames(frames, capacity=8):
+    """The frames a capacity-8 schedule holds after ``frames`` frames."""
+    from vmatting.plate import SampleSchedule
+    sched = SampleSchedule(capacity)
+    for t in range(frames):
+        sched.offer(t)
+    return sched.kept()
+
+
 # ---------------------------------------------------------------- end to end: a clip with nothing but its own frames
 
 def test_stream_over_the_estimated_plate(vgg0):

@@ -262,7 +262,7 @@ def test_scorer_device_tensors_and_reset(clip):
     assert np.isnan(plain.result()["clip"]["messddt"])
 
 
-def test_scorer_estimated_flows_equal_given_estimates():
+def test_scorer_estimated_flows_equal_given_estimates(monkeypatch):
     from vmatting import MatteScorer, ops
     n, opts = 5, {"warps": 2, "iters": 4}
     tex = fer.texture(H, W, 7)
@@ -274,11 +274,17 @@ def test_scorer_estimated_flows_equal_given_estimates():
     assert np.abs(flows[1:]).max() > 0.5
     given = MatteScorer(H, W, flow="given").add(pred, gt, None, flows).stats()
     assert (given[1:, 5] > 0).all()
+    pairs, from_pyramids = [], ops.flow_from_pyramids  # the pairs a scorer estimates: frame 0 of a clip has none
+    monkeypatch.setattr(ops, "flow_from_pyramids", lambda *a, **kw: pairs.append(1) or from_pyramids(*a, **kw))
     for sizes in ((n,), (2, 1, 2)):
         est = MatteScorer(H, W, flow="estimate", flow_options=opts)
-        for a, b in chunks(sizes):
-            est.add(pred[a:b], gt[a:b], None, None, cmp[a:b])
-        assert np.array_equal(bits(est.stats()), bits(given)), sizes
+        for clip in range(2):  # the second after reset(): frame 0 has no previous frame again, and its row no flow
+            del pairs[:]
+            for a, b in chunks(sizes):
+                est.add(pred[a:b], gt[a:b], None, None, cmp[a:b])
+            assert np.array_equal(bits(est.stats()), bits(given)), (sizes, clip)
+            assert len(pairs) == n - 1, (sizes, clip)
+            est.reset()
 
 
 def test_frame_stream_u8_mattes_feed_the_scorer(vgg0):

@@ -218,6 +218,12 @@ def test_wrappers_check_on_the_host():
     for bad in (clip.astype(np.float32), s, s[0], clip.tolist(), None):   # (s: a torch tensor on the host)
         with pytest.raises(TypeError):
             est.add(bad)
+    wide = torch.zeros((4, 5, 12, 3), dtype=torch.uint8)[:, :, ::2]       # strided, and on the host: the device is the fault
+    assert not wide.is_contiguous() and wide.shape == s.shape
+    with pytest.raises(TypeError):
+        est.add(wide)
+    with pytest.raises(TypeError):
+        reader.plate_from_clip(wide)
     for bad in (clip[:, :4], clip[..., :2], clip[0, 0], clip[None]):
         with pytest.raises(ValueError):
             est.add(bad)

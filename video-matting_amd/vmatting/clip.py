@@ -16,7 +16,7 @@ it in stream order overwrites that buffer with alpha[t].  A frame's compute chai
 quantise, download) is one HIP graph per slot, captured once over static buffers on one stream.
 
 The flows come from the caller, as in the reference's .flo files, or (``flow="estimate"``) from the frames themselves:
-ops.flow_pyramid of the frame and ops.flow_from_pyramids against the previous frame's pyramid head the frame's chain,
+the frame's pyramid and its flows against the previous frame's pyramid (flow_track.FlowTracker) head the frame's chain,
 and nothing is staged or uploaded for the flows.  The matte before the first frame comes from the caller (for example
 a key frame's matte by UNetVideo).
 """
@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .flow_track import FlowTracker
 from .pipeline import PER_FRAME, Slot, SlotPipeline, check_new_bg, check_out, check_static_bg
 from .unet_simple import UNetSimple
 
@@ -98,13 +99,10 @@ class ClipStream(SlotPipeline):
         thresh = float(thresh)
         if not thresh >= 0.0:
             raise ValueError("ClipStream: thresh must be a non-negative number, got %r" % (thresh,))
-        if flow not in ops.FLOW_MODES:
-            raise ValueError("ClipStream: flow must be one of %s, got %r" % (ops.FLOW_MODES, flow))
-        self.estimate = flow == "estimate"
-        if flow_options is not None and not self.estimate:
-            raise ValueError("ClipStream: flow_options go with flow='estimate'")
+        flow_options = ops.check_flow_mode("ClipStream", flow, flow_options, h, w)
+        self.estimate = flow_options is not None
         if self.estimate:
-            self.flow_options = ops.flow_options("ClipStream: flow_options", h, w, flow_options)
+            self.flow_options = flow_options
         static_bg = check_static_bg("ClipStream", static_bg, h, w)
         self.new_bg = check_new_bg("ClipStream", out, new_bg, h, w)
         self.model, self.h, self.w, self.depth = model, h, w, depth
@@ -113,7 +111,7 @@ class ClipStream(SlotPipeline):
         self.reuse_bg_tower = bool(reuse_bg_tower) and static_bg is not None
         self.device = model.device
         self.stats = {"bg_tower_evals": 0, "frames": 0}
-        self._plate = self._new_plate = self._buf = None
+        self._buf = None
         self._cmp0 = self._bw = self._fw = None
 
     # ------------------------------------------------------------------ checks (host only)
@@ -132,26 +130,19 @@ class ClipStream(SlotPipeline):
             raise ValueError("ClipStream: bg is None exactly when a static_bg was given")
         if (fw is None) == self.occlusion and not self.estimate:
             raise ValueError("ClipStream: forward is None exactly when occlusion=False")
-        for name, a, dt, c in (("cmp", cmp, np.uint8, 3), ("bg", bg, np.uint8, 3), ("backward", bw, np.float32, 2),
-                               ("forward", fw, np.float32, 2)) + ((("new_bg", item[4], np.uint8, 3),) if per_frame else ()):
+        arrays = [("cmp", cmp, torch.uint8, "h,w,3"), ("bg", bg, torch.uint8, "h,w,3"),
+                  ("backward", bw, torch.float32, "h,w,2"), ("forward", fw, torch.float32, "h,w,2")]
+        if per_frame:
+            arrays.append(("new_bg", item[4], torch.uint8, "h,w,3"))
+        for name, a, dt, shape in arrays:
             if a is None and (name in ("bg", "forward") or self.estimate and name == "backward"):
                 continue
-            if not isinstance(a, np.ndarray):
-                raise TypeError("ClipStream: %s must be a numpy array, got %s" % (name, type(a).__name__))
-            if a.dtype != dt:
-                raise TypeError("ClipStream: %s must be %s, got %s" % (name, np.dtype(dt).name, a.dtype))
-            if a.shape != (self.h, self.w, c):
-                raise ValueError("ClipStream: %s must be [h,w,%d] = %s, got %s" % (name, c, (self.h, self.w, c), a.shape))
+            ops.check_array("ClipStream", name, a, (dt,), shape, h=self.h, w=self.w)
         return (cmp, bg, bw, fw, item[4]) if per_frame else (cmp, bg, bw, fw)
 
     def check_alpha0(self, alpha0):
         """The matte before the first frame as f32 [h,w]: f32 as it is, uint8 as f32(u / 255.0) (reader.py:16)."""
-        if not isinstance(alpha0, np.ndarray):
-            raise TypeError("ClipStream: alpha0 must be a numpy array, got %s" % type(alpha0).__name__)
-        if alpha0.dtype not in (np.dtype(np.float32), np.dtype(np.uint8)):
-            raise TypeError("ClipStream: alpha0 must be float32 or uint8, got %s" % alpha0.dtype)
-        if alpha0.shape != (self.h, self.w):
-            raise ValueError("ClipStream: alpha0 must be [h,w] = %s, got %s" % ((self.h, self.w), alpha0.shape))
+        ops.check_array("ClipStream", "alpha0", alpha0, (torch.float32, torch.uint8), "h,w", h=self.h, w=self.w)
         if alpha0.dtype == np.uint8:
             return (alpha0.astype(np.float64) / 255.0).astype(np.float32)
         return np.ascontiguousarray(alpha0)
@@ -168,19 +159,13 @@ class ClipStream(SlotPipeline):
         self._buf = self.model._buffers(1, self.h, self.w)
         self._views = self.model.feed_views(1, self.h, self.w)
         self._alpha = self._buf["out"]
-        if self.static_bg is not None:
-            self._plate = torch.from_numpy(self.static_bg).to(dev)
-        if isinstance(self.new_bg, np.ndarray):
-            self._new_plate = torch.from_numpy(self.new_bg).to(dev)
+        self._upload_plates()
         if self.estimate:
             # one set of flow buffers for every slot (the chains run one after another on the compute stream), and
-            # the two pyramids at fixed addresses: every slot's graph reads the previous frame's and leaves its own there
-            o = self.flow_options
+            # the tracker's pyramids at fixed addresses: every slot's graph reads the previous frame's and leaves its own
             f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
             self._bw, self._fw = f32(1, self.h, self.w, 2), f32(1, self.h, self.w, 2) if self.occlusion else None
-            self._pyr_cur, self._pyr_prev = (f32(ops.flow_pyramid_floats(self.h, self.w, o["levels"])) for _ in range(2))
-            self._flow_work = torch.zeros(ops.flow_workspace_bytes(self.h, self.w, o["levels"]), dtype=torch.uint8,
-                                          device=dev)
+            self._flow = FlowTracker(self.h, self.w, self.flow_options, dev)
             self._d_cmp0 = torch.zeros((self.h, self.w, 3), dtype=torch.uint8, device=dev)
         self._slots = [_Slot(self) for _ in range(self.depth)]
         torch.cuda.synchronize(dev)  # the plate and the zeroed buffers, before another stream touches them
@@ -202,37 +187,22 @@ class ClipStream(SlotPipeline):
             self._alpha.copy_(torch.from_numpy(self._alpha0).view(1, self.h, self.w, 1))
             if self._cmp0 is not None:  # the previous frame of the first one
                 self._d_cmp0.copy_(torch.from_numpy(self._cmp0))
-                self._pyramid(self._d_cmp0, self._pyr_prev)
+                self._flow.seed(self._d_cmp0)
 
     def _download(self, s):
         """The slot's result from the model's output buffer (and, composed, the slot's uint8 inputs), which it only
         reads."""
-        s.download(self._alpha, s.d_cmp, self._plate if self._plate is not None else s.d_bg,
-                   self._new_plate if self._new_plate is not None else s.d_nw)
-
-    def _pyramid(self, frame, out):
-        ops.flow_pyramid(frame, self.flow_options["levels"], out=out, work=self._flow_work)
-
-    def _estimate(self, s):
-        """This frame's pyramid, its flows against the previous frame's, and this frame's pyramid left as the
-        previous one for the next chain."""
-        o = self.flow_options
-        self._pyramid(s.d_cmp[0], self._pyr_cur)
-        for out, a, b in ((self._bw, self._pyr_cur, self._pyr_prev), (self._fw, self._pyr_prev, self._pyr_cur)):
-            if out is not None:
-                ops.flow_from_pyramids(a, b, self.h, self.w, o["levels"], o["warps"], o["iters"], o["alpha"], out=out[0],
-                                       work=self._flow_work)
-        self._pyr_prev.copy_(self._pyr_cur)
+        s.download(self._alpha, s.d_cmp, *self._plates(s, 1))
 
     def _feed(self, s):
         if s.flag is not None:
             s.flag.zero_()
         towers, cat = self._views
-        if self.estimate:
-            self._estimate(s)
+        if self.estimate:  # this frame's flows against the previous frame, and its pyramid left for the next chain
+            self._flow.advance(s.d_cmp, self._bw, self._fw)
         bw, fw = (self._bw, self._fw) if self.estimate else (s.d_bw, s.d_fw)
-        ops.clip_feed(s.d_cmp, self._plate if self._plate is not None else s.d_bg, self._alpha, bw, fw,
-                      self.thresh, self.promote, towers=towers, cat=cat, err=s.flag)
+        ops.clip_feed(s.d_cmp, self._plates(s, 1)[0], self._alpha, bw, fw, self.thresh, self.promote, towers=towers,
+                      cat=cat, err=s.flag)
 
     def _submit(self, s, index, cmp, bg, bw, fw, nw=None):
         s.index = index
@@ -247,7 +217,7 @@ class ClipStream(SlotPipeline):
         with torch.cuda.stream(self._compute):
             self._compute.wait_event(s.uploaded)
             if self.estimate and index == 0 and self._cmp0 is None:  # alpha0 belongs to this frame: zero flows
-                self._pyramid(s.d_cmp[0], self._pyr_prev)
+                self._flow.seed(s.d_cmp[0])
             if self.graph:
                 s.graphs[towers].replay()
             else:

@@ -877,27 +877,62 @@ def _parse_shapes(shapes):
     return tuple(tuple(int(d) if d.isdigit() else d for d in s.strip().split(",")) for s in shapes.split("|"))
 
 
+def _match_shape(who, name, shape, shapes, dims):
+    """``shape`` is one of ``shapes`` -> that shape, as ints; a ValueError otherwise.  ``shapes``: alternatives like
+    "n,h,w | n,h,w,1"; a number stands for itself, a letter for the size ``dims`` gives it or, where it gives none, for
+    any size >= 1."""
+    shape = tuple(int(v) for v in shape)
+    for spec in _parse_shapes(shapes):
+        if len(spec) == len(shape) and all(v == dims[d] if d in dims else v >= 1 if isinstance(d, str) else v == d
+                                           for v, d in zip(shape, spec)):
+            return shape
+    sizes = ", ".join("%s=%d" % kv for kv in dims.items())
+    raise ValueError("%s: %s must be %s%s, got %s" % (who, name, " or ".join("[%s]" % s.strip() for s in
+                                                                             shapes.split("|")),
+                                                      " with " + sizes if sizes else "", shape))
+
+
 def _check_tensor(who, name, t, dtypes, shapes, wrong=TypeError, **dims):
-    """``t`` is a contiguous torch tensor of one of ``dtypes`` whose shape is one of ``shapes`` -> that shape, as ints.
-    ``shapes``: alternatives like "n,h,w | n,h,w,1"; a number stands for itself, a letter for the size ``dims`` gives it
-    or, where it gives none, for any size >= 1.  ``wrong``: what a non-tensor or another dtype raises; a shape or strides
-    raise ValueError.  The device is never looked at: _require_gpu is every op's last check."""
+    """``t`` is a contiguous torch tensor of one of ``dtypes`` whose shape is one of ``shapes`` (_match_shape's grammar)
+    -> that shape, as ints.  ``wrong``: what a non-tensor or another dtype raises; a shape or strides raise ValueError.
+    The device is never looked at: _require_gpu is every op's last check."""
     if not isinstance(t, torch.Tensor):
         raise wrong("%s: %s must be a torch tensor, got %s" % (who, name, type(t).__name__))
     if t.dtype not in dtypes:
         raise wrong("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
-    shape = tuple(int(v) for v in t.shape)
-    for spec in _parse_shapes(shapes):
-        if len(spec) == len(shape) and all(v == dims[d] if d in dims else v >= 1 if isinstance(d, str) else v == d
-                                           for v, d in zip(shape, spec)):
-            break
-    else:
-        sizes = ", ".join("%s=%d" % kv for kv in dims.items())
-        raise ValueError("%s: %s must be %s%s, got %s" % (who, name, " or ".join("[%s]" % s.strip() for s in
-                                                                                 shapes.split("|")),
-                                                          " with " + sizes if sizes else "", shape))
+    shape = _match_shape(who, name, t.shape, shapes, dims)
     if not t.is_contiguous():
         raise ValueError("%s: %s must be contiguous" % (who, name))
+    return shape
+
+
+# what the layer above the ops takes from its callers: host arrays, device tensors, or either
+NUMPY, DEVICE, EITHER = "a numpy array", "a ROCm device tensor", "a numpy array or a ROCm device tensor"
+NUMPY_DTYPES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.float32): torch.float32,
+                np.dtype(np.float64): torch.float64}  # the one numpy -> torch dtype table
+
+
+def torch_dtype(a):
+    """The torch dtype of a tensor or a numpy array (a numpy dtype without a torch twin here stays what it is)."""
+    return a.dtype if isinstance(a, torch.Tensor) else NUMPY_DTYPES.get(a.dtype, a.dtype)
+
+
+def check_array(who, name, a, dtypes, shapes, accept=NUMPY, wrong=TypeError, strided=False, **dims):
+    """_check_tensor's sibling for the streams and conveniences: ``a`` is what ``accept`` names (NUMPY, DEVICE or
+    EITHER), of one of the torch ``dtypes`` (torch_dtype) and one of ``shapes`` (_match_shape's grammar) -> that shape,
+    as ints.  ``wrong``: what another type, another dtype and a tensor on the host raise; a shape or a tensor's strides
+    raise ValueError.  ``strided``: the consumer copies the tensor, so any strides are taken (a numpy array's always
+    are: it is staged or uploaded).  A tensor's device is looked at last, so every other fault shows without one."""
+    tensor = isinstance(a, torch.Tensor)
+    if not (tensor and accept != NUMPY or isinstance(a, np.ndarray) and accept != DEVICE):
+        raise wrong("%s: %s must be %s, got %s" % (who, name, accept, type(a).__name__))
+    if torch_dtype(a) not in dtypes:
+        raise wrong("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), a.dtype))
+    shape = _match_shape(who, name, a.shape, shapes, dims)
+    if tensor and not strided and not a.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+    if tensor and not a.is_cuda:
+        raise wrong("%s: %s is a host tensor; pass %s" % (who, name, accept))
     return shape
 
 
@@ -941,23 +976,6 @@ def _options(who, defaults, options, check, *args):
 
 
 # ---------------------------------------------------------------- inference on a decoded clip
-
-def _check_u8_frames(cmp, bg, trimap):
-    """Shapes / dtypes of decoded frames (torch tensors or numpy arrays): cmp u8 [n,h,w,3], bg u8 [n,h,w,3] | [1,h,w,3] |
-    [h,w,3], trimap u8 [n,h,w] | None -> (n, h, w, nb)."""
-    for name, t in (("cmp", cmp), ("bg", bg), ("trimap", trimap)):
-        if t is not None and str(t.dtype).split(".")[-1] != "uint8":
-            raise TypeError("%s must be uint8, got %s" % (name, t.dtype))
-    if len(cmp.shape) != 4 or cmp.shape[3] != 3 or cmp.shape[0] < 1:
-        raise ValueError("cmp must be [n,h,w,3] BGR, got %s" % (tuple(cmp.shape),))
-    n, h, w, _ = (int(v) for v in cmp.shape)
-    if tuple(bg.shape) not in ((n, h, w, 3), (1, h, w, 3), (h, w, 3)):
-        raise ValueError("bg must be [n,h,w,3], or one [h,w,3] plate, for cmp %s; got %s" %
-                         (tuple(cmp.shape), tuple(bg.shape)))
-    if trimap is not None and tuple(trimap.shape) != (n, h, w):
-        raise ValueError("trimap must be [n,h,w] = %s, got %s" % ((n, h, w), tuple(trimap.shape)))
-    return n, h, w, (n if tuple(bg.shape) == (n, h, w, 3) else 1)
-
 
 def frame_buffer(model, n, h, w, native=None):
     """An [n,h,w,IN_CH] input-frame buffer for ``model``: ``native`` (default: a plain bf16 model) gives bf16 pixels 8
@@ -1111,6 +1129,19 @@ def flow_options(who, h, w, options):
     """A dict over FLOW_DEFAULTS (None: the defaults), checked for [h,w] frames -> {"levels": ..., "warps": ...,
     "iters": ..., "alpha": ...}."""
     return _options(who, FLOW_DEFAULTS, options, check_flow_options, h, w)
+
+
+def check_flow_mode(who, flow, options, h, w, modes=FLOW_MODES, default=None):
+    """The ``flow`` argument of FrameStream, ClipStream and MatteScorer: one of the ``modes`` this caller allows (None,
+    where allowed, stands for ``default``), and their ``flow_options`` (a dict over FLOW_DEFAULTS) only with "estimate"
+    -> the options checked for [h,w] frames, or None in every other mode."""
+    if flow not in modes:
+        raise ValueError("%s: flow must be one of %s, got %r" % (who, list(modes), flow))
+    if (default if flow is None else flow) != "estimate":
+        if options is not None:
+            raise ValueError("%s: flow_options go with flow='estimate'" % who)
+        return None
+    return flow_options("%s: flow_options" % who, h, w, options)
 
 
 def flow_workspace_bytes(h, w, levels=6):

@@ -29,10 +29,7 @@ def check_static_bg(who, static_bg, h, w, name="static_bg"):
     if static_bg is None:
         return None
     static_bg = np.asarray(static_bg)
-    if static_bg.dtype != np.uint8:
-        raise TypeError("%s: %s must be uint8, got %s" % (who, name, static_bg.dtype))
-    if static_bg.shape != (h, w, 3):
-        raise ValueError("%s: %s must be [h,w,3] = %s, got %s" % (who, name, (h, w, 3), static_bg.shape))
+    ops.check_array(who, name, static_bg, (torch.uint8,), "h,w,3", h=h, w=w)
     return np.ascontiguousarray(static_bg)
 
 
@@ -107,7 +104,8 @@ class SlotPipeline:
 
     check_item(item) -> args   host-only validation of one source item, before any device work for it
     _needs_setup()             True until _setup() has built ``_slots`` (a list of ``depth`` slots)
-    _setup()                   streams (_make_streams), slots and whatever else the first valid item needs
+    _setup()                   streams (_make_streams), plates (_upload_plates), slots and whatever else the first
+                               valid item needs
     _begin()                   before the first item of a run is submitted; here: the compute stream waits on what
                                the caller queued
     _submit(slot, index, *args) stage, upload and queue the compute chain of one item
@@ -119,6 +117,8 @@ class SlotPipeline:
     depth = 1
     _slots = None   # built with the first valid item: nothing touches the device before that
     _upload = _compute = None
+    static_bg = new_bg = None      # check_static_bg's and check_new_bg's results
+    _plate = _new_plate = None     # ... and the plates among them on the device, once _setup() has run
 
     def check_item(self, item):
         raise NotImplementedError
@@ -128,6 +128,19 @@ class SlotPipeline:
 
     def _make_streams(self):
         self._upload, self._compute = torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device)
+
+    def _upload_plates(self):
+        """The static background and a new plate, where the stream was given them, to the device."""
+        if self.static_bg is not None:
+            self._plate = torch.from_numpy(self.static_bg).to(self.device)
+        if isinstance(self.new_bg, np.ndarray):
+            self._new_plate = torch.from_numpy(self.new_bg).to(self.device)
+
+    def _plates(self, s, k):
+        """(background, new background | None) of the slot's first k frames: the plate, or the slot's per-frame
+        copies."""
+        return (self._plate if self._plate is not None else s.d_bg[:k],
+                self._new_plate if self._new_plate is not None else None if s.d_nw is None else s.d_nw[:k])
 
     def _begin(self):
         self._compute.wait_stream(torch.cuda.current_stream(self.device))

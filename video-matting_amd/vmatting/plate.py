@@ -86,18 +86,10 @@ class PlateEstimator:
 
     def _check(self, frames):
         import torch
-        who = "PlateEstimator.add"
-        device = isinstance(frames, torch.Tensor)
-        if not device and not isinstance(frames, np.ndarray):
-            raise TypeError("%s: frames must be a numpy array or a device tensor, got %s" % (who, type(frames).__name__))
-        if device and not frames.is_cuda:
-            raise TypeError("%s: a torch tensor must be on the device, got %s" % (who, frames.device))
-        if str(frames.dtype).split(".")[-1] != "uint8":
-            raise TypeError("%s: frames must be uint8, got %s" % (who, frames.dtype))
-        shape = tuple(frames.shape)
-        if shape[-3:] != (self.h, self.w, 3) or len(shape) not in (3, 4):
-            raise ValueError("%s: frames must be [k,h,w,3] or [h,w,3] with h, w = %d, %d; got %s"
-                             % (who, self.h, self.w, shape))
+        from . import ops
+        # (any strides: add() copies the frames the schedule keeps, one by one)
+        shape = ops.check_array("PlateEstimator.add", "frames", frames, (torch.uint8,), "k,h,w,3 | h,w,3", ops.EITHER,
+                                strided=True, h=self.h, w=self.w)
         return frames[None] if len(shape) == 3 else frames
 
     def add(self, frames_u8):

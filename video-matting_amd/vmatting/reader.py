@@ -53,23 +53,40 @@ def create_composite_image(fg, bg, alpha, out_dtype=torch.float64):
     return a * np.asarray(fg) + (1.0 - a) * np.asarray(bg)
 
 
+U8 = (torch.uint8,)
+
+
+def _stack(a, single=True):
+    """``a``, one frame (``single``) or a stack of them, checked already, as a contiguous device tensor with a leading
+    frame axis: a host array is uploaded, a device tensor stays on its device (made contiguous where it is not)."""
+    if isinstance(a, torch.Tensor):
+        a = a.contiguous()
+    else:
+        a = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return a[None] if single else a
+
+
+def _like(out, given, single):
+    """A device result with a leading frame axis as what the caller gave: its one frame for one frame (``single``), a
+    numpy array for a numpy array."""
+    out = out[0] if single else out
+    return out if isinstance(given, torch.Tensor) else out.cpu().numpy()
+
+
 def _compose_frame(cmp, bg, alpha, new_bg, mode):
     """One host frame through ops.matte_compose: uint8 [h,w,3] cmp / bg (/ new_bg), alpha f32 or f64 [h,w]."""
     from vmatting import ops
-    alpha = np.asarray(alpha)
-    if alpha.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-        raise TypeError("alpha must be float32 or float64, got %s" % alpha.dtype)
-    planes = [np.asarray(a) for a in (cmp, bg) + (() if new_bg is None else (new_bg,))]
-    for name, a in zip(("cmp", "bg", "new_bg"), planes):
-        if a.dtype != np.uint8:
-            raise TypeError("%s must be uint8, got %s" % (name, a.dtype))
-        if a.ndim != 3 or a.shape[2] != 3 or a.shape != planes[0].shape:
-            raise ValueError("%s must be [h,w,3] like cmp %s, got %s" % (name, planes[0].shape, a.shape))
-    if alpha.shape != planes[0].shape[:2]:
-        raise ValueError("alpha must be [h,w] = %s, got %s" % (planes[0].shape[:2], alpha.shape))
-    dev = [torch.from_numpy(np.ascontiguousarray(a)[None]).cuda() for a in planes]
-    a32 = torch.from_numpy(np.ascontiguousarray(alpha.astype(np.float32))[None]).cuda()
-    return ops.matte_compose(a32, dev[0], dev[1], dev[2] if len(dev) == 3 else None, mode=mode)[0].cpu().numpy()
+    who = "replace_background" if mode == "over" else "estimate_foreground"
+    alpha, cmp, bg = np.asarray(alpha), np.asarray(cmp), np.asarray(bg)
+    h, w, _ = ops.check_array(who, "cmp", cmp, U8, "h,w,3")
+    ops.check_array(who, "bg", bg, U8, "h,w,3", h=h, w=w)
+    if new_bg is not None:
+        new_bg = np.asarray(new_bg)
+        ops.check_array(who, "new_bg", new_bg, U8, "h,w,3", h=h, w=w)
+    ops.check_array(who, "alpha", alpha, (torch.float32, torch.float64), "h,w", h=h, w=w)
+    a32 = _stack(np.asarray(alpha, np.float32))  # (f64 rounded to f32; f32 as it is)
+    out = ops.matte_compose(a32, _stack(cmp), _stack(bg), None if new_bg is None else _stack(new_bg), mode=mode)
+    return _like(out, alpha, True)
 
 
 def estimate_foreground(cmp, bg, alpha, premultiplied=False):
@@ -99,25 +116,15 @@ def score_matte(pred, gt, trimap=None):
     out, through the vm_matte_score kernel (include/vmatting.h; published tables quote SAD / 1000, MSE * 1000 and
     Grad / 1000).  A clip, and its temporal metrics, go through vmatting.MatteScorer."""
     from vmatting import ops
-    planes = []
-    for name, a in (("pred", pred), ("gt", gt)):
-        a = np.asarray(a)
-        if a.dtype == np.float64:
-            a = a.astype(np.float32)
-        if a.dtype not in (np.dtype(np.float32), np.dtype(np.uint8)):
-            raise TypeError("%s must be float32, float64 or uint8, got %s" % (name, a.dtype))
-        if a.ndim != 2 or a.size == 0 or a.shape != np.shape(pred):
-            raise ValueError("%s must be [h,w] like pred %s, got %s" % (name, np.shape(pred), a.shape))
-        planes.append(a)
+    who, matte = "score_matte", (torch.float32, torch.float64, torch.uint8)
+    pred, gt = np.asarray(pred), np.asarray(gt)
+    h, w = ops.check_array(who, "pred", pred, matte, "h,w")
+    ops.check_array(who, "gt", gt, matte, "h,w", h=h, w=w)
     if trimap is not None:
         trimap = np.asarray(trimap)
-        if trimap.dtype != np.uint8:
-            raise TypeError("trimap must be uint8, got %s" % trimap.dtype)
-        if trimap.shape != planes[0].shape:
-            raise ValueError("trimap must be [h,w] = %s, got %s" % (planes[0].shape, trimap.shape))
-        planes.append(trimap)
-    dev = [torch.from_numpy(np.ascontiguousarray(a)[None]).cuda() for a in planes]
-    res = ops.score_summary(ops.matte_score(dev[0], dev[1], dev[2] if len(dev) == 3 else None))
+        ops.check_array(who, "trimap", trimap, U8, "h,w", h=h, w=w)
+    pred, gt = (a.astype(np.float32) if a.dtype == np.float64 else a for a in (pred, gt))
+    res = ops.score_summary(ops.matte_score(_stack(pred), _stack(gt), None if trimap is None else _stack(trimap)))
     return {k: float(res[k][0]) for k in ("count", "sad", "mse", "grad")}
 
 
@@ -132,20 +139,11 @@ def upsample_matte(alpha_lo, cmp_u8, scale, **options):
     scale = ops.check_scale(who, scale)
     opts = ops.guided_options(who, options)
     alpha_lo, cmp_u8 = np.asarray(alpha_lo), np.asarray(cmp_u8)
-    if alpha_lo.dtype == np.float64:
-        alpha_lo = alpha_lo.astype(np.float32)
-    if alpha_lo.dtype != np.float32:
-        raise TypeError("%s: alpha_lo must be float32 or float64, got %s" % (who, alpha_lo.dtype))
-    if cmp_u8.dtype != np.uint8:
-        raise TypeError("%s: cmp must be uint8, got %s" % (who, cmp_u8.dtype))
-    if cmp_u8.ndim != 3 or cmp_u8.shape[2] != 3 or cmp_u8.size == 0:
-        raise ValueError("%s: cmp must be [h,w,3] BGR, got %s" % (who, cmp_u8.shape))
-    lo = ops.reduced_size(cmp_u8.shape[0], cmp_u8.shape[1], scale)
-    if alpha_lo.shape != lo:
-        raise ValueError("%s: alpha_lo must be [hm,wm] = %s for cmp %s at scale %d, got %s" %
-                         (who, lo, cmp_u8.shape, scale, alpha_lo.shape))
-    dev = [torch.from_numpy(np.ascontiguousarray(a)[None]).cuda() for a in (alpha_lo, cmp_u8)]
-    return ops.guided_upsample(dev[0], dev[1], scale, **opts)[0, :, :, 0].cpu().numpy()
+    h, w, _ = ops.check_array(who, "cmp", cmp_u8, U8, "h,w,3")
+    hm, wm = ops.reduced_size(h, w, scale)  # (ceil(h / scale), ceil(w / scale))
+    ops.check_array(who, "alpha_lo", alpha_lo, (torch.float32, torch.float64), "hm,wm", hm=hm, wm=wm)
+    out = ops.guided_upsample(_stack(np.asarray(alpha_lo, np.float32)), _stack(cmp_u8), scale, **opts)
+    return _like(out[..., 0], alpha_lo, True)
 
 
 def fill_enclosed(trimap_u8, max_area=0):
@@ -156,21 +154,12 @@ def fill_enclosed(trimap_u8, max_area=0):
     uint8, one frame [H,W] or a stack [N,H,W]; numpy arrays return numpy, device tensors stay on the device."""
     from vmatting import ops
     who = "fill_enclosed"
-    device = isinstance(trimap_u8, torch.Tensor)
-    if not device:
-        trimap_u8 = np.ascontiguousarray(trimap_u8)
-    if trimap_u8.dtype not in (torch.uint8, np.dtype(np.uint8)):
-        raise TypeError("%s: the trimap must be uint8, got %s" % (who, trimap_u8.dtype))
-    if len(trimap_u8.shape) not in (2, 3) or min(trimap_u8.shape) < 1:
-        raise ValueError("%s: the trimap must be [H,W] or [N,H,W], got %s" % (who, tuple(trimap_u8.shape)))
+    if not isinstance(trimap_u8, torch.Tensor):
+        trimap_u8 = np.asarray(trimap_u8)
+    shape = ops.check_array(who, "the trimap", trimap_u8, U8, "H,W | N,H,W", ops.EITHER, strided=True)
+    single = len(shape) == 2
     max_area = ops.check_int(who, "max_area", max_area, 0)
-    single = len(trimap_u8.shape) == 2
-    tri = trimap_u8[None] if single else trimap_u8
-    if device:
-        out = ops.trimap_fill_enclosed(tri.contiguous(), max_area)
-    else:
-        out = ops.trimap_fill_enclosed(torch.from_numpy(tri).cuda(), max_area).cpu().numpy()
-    return out[0] if single else out
+    return _like(ops.trimap_fill_enclosed(_stack(trimap_u8, single), max_area), trimap_u8, single)
 
 
 def match_plate(cmp_u8, bg_u8, **options):
@@ -184,18 +173,12 @@ def match_plate(cmp_u8, bg_u8, **options):
     who = "match_plate"
     opts = ops.gain_options(who, options)
     cmp_u8, bg_u8 = np.asarray(cmp_u8), np.asarray(bg_u8)
-    for name, a in (("cmp", cmp_u8), ("bg", bg_u8)):
-        if a.dtype != np.uint8:
-            raise TypeError("%s: %s must be uint8, got %s" % (who, name, a.dtype))
-    if cmp_u8.ndim != 3 or cmp_u8.shape[2] != 3 or cmp_u8.size == 0:
-        raise ValueError("%s: cmp must be [h,w,3] BGR, got %s" % (who, cmp_u8.shape))
-    if bg_u8.shape != cmp_u8.shape:
-        raise ValueError("%s: bg must be [h,w,3] like cmp %s, got %s" % (who, cmp_u8.shape, bg_u8.shape))
-    cmp, bg = (torch.from_numpy(np.ascontiguousarray(a)[None]).cuda() for a in (cmp_u8, bg_u8))
+    h, w, _ = ops.check_array(who, "cmp", cmp_u8, U8, "h,w,3")
+    ops.check_array(who, "bg", bg_u8, U8, "h,w,3", h=h, w=w)
+    cmp, bg = _stack(cmp_u8), _stack(bg_u8)
     gain, support = ops.plate_gain_fit(cmp, bg, **opts)
-    plate = ops.plate_gain_apply(bg, gain)
-    return (plate[0].cpu().numpy(), gain[0].cpu().numpy().astype(np.float32) / np.float32(ops.GAIN_ONE),
-            support[0].cpu().numpy().astype(np.int64))
+    plate, gain, support = (_like(t, cmp_u8, True) for t in (ops.plate_gain_apply(bg, gain), gain, support))
+    return plate, gain.astype(np.float32) / np.float32(ops.GAIN_ONE), support.astype(np.int64)
 
 
 def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, fill=None, gain=None,
@@ -218,26 +201,22 @@ def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, 
         raise TypeError("%s: cmp and bg are both numpy arrays or both torch tensors" % who)
     given = {"lo": lo, "hi": hi, "r_bg": r_bg, "r_fg": r_fg}
     opts = ops.plate_options(who, {k: v for k, v in given.items() if v is not None})
-    device = isinstance(cmp_u8, torch.Tensor)
-    if not device:
-        cmp_u8, bg_u8 = np.ascontiguousarray(cmp_u8), np.ascontiguousarray(bg_u8)
-    single = len(cmp_u8.shape) == 3
-    cmp = cmp_u8[None] if single else cmp_u8
-    if single and len(bg_u8.shape) != 3:
-        raise ValueError("%s: one [H,W,3] frame takes one [H,W,3] plate, got %s" % (who, tuple(bg_u8.shape)))
-    ops._check_u8_frames(cmp, bg_u8, None)
-    if device:
-        cmp, bg = cmp.contiguous(), bg_u8.contiguous()
+    if not isinstance(cmp_u8, torch.Tensor):
+        cmp_u8, bg_u8 = np.asarray(cmp_u8), np.asarray(bg_u8)
+    shape = ops.check_array(who, "cmp", cmp_u8, U8, "H,W,3 | N,H,W,3", ops.EITHER, strided=True)
+    single = len(shape) == 3
+    if single:  # one [H,W,3] frame takes one [H,W,3] plate
+        ops.check_array(who, "bg", bg_u8, U8, "H,W,3", ops.EITHER, strided=True, H=shape[0], W=shape[1])
     else:
-        cmp, bg = torch.from_numpy(cmp).cuda(), torch.from_numpy(bg_u8).cuda()
+        ops.check_array(who, "bg", bg_u8, U8, "N,H,W,3 | 1,H,W,3 | H,W,3", ops.EITHER, strided=True, N=shape[0],
+                        H=shape[1], W=shape[2])
+    cmp, bg = _stack(cmp_u8, single), _stack(bg_u8, False)
     if gopts is not None:
         bg = ops.plate_gain_apply(bg, ops.plate_gain_fit(cmp, bg, **gopts)[0])
     out = ops.trimap_from_plate(cmp, bg, **opts)
     if cap is not None:
         ops.trimap_fill_enclosed(out, cap, out=out)
-    if not device:
-        out = out.cpu().numpy()
-    return out[0] if single else out
+    return _like(out, cmp_u8, single)
 
 
 def plate_from_clip(frames_u8, capacity=64, every=1):
@@ -248,19 +227,11 @@ def plate_from_clip(frames_u8, capacity=64, every=1):
     plate is not to be trusted (ops.plate_from_samples, include/vmatting.h).  No exposure or flicker compensation.
     numpy arrays return numpy, device tensors stay on the device."""
     from vmatting.plate import PlateEstimator
-    who = "plate_from_clip"
-    if not isinstance(frames_u8, (np.ndarray, torch.Tensor)):
-        raise TypeError("%s: frames must be a numpy array or a device tensor, got %s" % (who, type(frames_u8).__name__))
-    if str(frames_u8.dtype).split(".")[-1] != "uint8":
-        raise TypeError("%s: frames must be uint8, got %s" % (who, frames_u8.dtype))
-    shape = tuple(frames_u8.shape)
-    if len(shape) != 4 or shape[3] != 3 or min(shape) < 1:
-        raise ValueError("%s: frames must be [N,H,W,3] BGR, got %s" % (who, shape))
-    est = PlateEstimator(shape[1], shape[2], capacity, every)
-    plate, spread = est.add(frames_u8).result()
-    if isinstance(frames_u8, torch.Tensor):
-        return plate, spread
-    return plate.cpu().numpy(), spread.cpu().numpy()
+    from vmatting import ops
+    # (the clip's size for the estimator, whose add() copies the frames it keeps: any strides)
+    _, h, w, _ = ops.check_array("plate_from_clip", "frames", frames_u8, U8, "N,H,W,3", ops.EITHER, strided=True)
+    plate, spread = PlateEstimator(h, w, capacity, every).add(frames_u8).result()
+    return _like(plate, frames_u8, False), _like(spread, frames_u8, False)
 
 
 def read_fg_img(img_path):

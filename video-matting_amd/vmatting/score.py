@@ -18,16 +18,6 @@ from . import ops
 FLOW_MODES = (None,) + ops.FLOW_MODES
 
 
-def _dtype_of(a):
-    """The torch dtype of a numpy array or a tensor, None for anything else."""
-    if isinstance(a, torch.Tensor):
-        return a.dtype
-    if isinstance(a, np.ndarray):
-        return {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8,
-                np.dtype(np.float64): torch.float64}.get(a.dtype, a.dtype)
-    return None
-
-
 class MatteScorer:
     """SAD, MSE, gradient error, dtSSD and MESSDdt of predicted mattes against ground truth over a clip of [h,w] frames.
 
@@ -38,17 +28,11 @@ class MatteScorer:
 
     def __init__(self, h, w, device="cuda", flow=None, flow_options=None):
         self.h, self.w = ops.check_int("MatteScorer", "h", h, 1), ops.check_int("MatteScorer", "w", w, 1)
-        if flow not in FLOW_MODES:
-            raise ValueError("MatteScorer: flow must be one of %s, got %r" % (list(FLOW_MODES), flow))
-        if flow_options is not None and flow != "estimate":
-            raise ValueError("MatteScorer: flow_options go with flow='estimate'")
-        self.flow = flow
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("MatteScorer: a ROCm device is required, got %r" % (device,))
-        self.flow_options = None
-        if flow == "estimate":
-            self.flow_options = ops.flow_options("MatteScorer: flow_options", self.h, self.w, flow_options)
+        self.flow_options = ops.check_flow_mode("MatteScorer", flow, flow_options, self.h, self.w, FLOW_MODES)
+        self.flow = flow
         self._work = self._pyr = self._flow_work = None
         self.reset()
 
@@ -64,39 +48,18 @@ class MatteScorer:
     # ------------------------------------------------------------------------------------------ host-side checks
     def check_chunk(self, pred, gt, trimap=None, backward=None, cmp=None):
         """Types, dtypes and shapes of one add(), on the host -> k."""
-        who = "MatteScorer.add"
-        dp = _dtype_of(pred)
-        if dp is None:
-            raise TypeError("%s: pred must be a numpy array or a torch tensor, got %s" % (who, type(pred).__name__))
-        if len(pred.shape) != 3 or tuple(pred.shape[1:]) != (self.h, self.w) or pred.shape[0] < 1:
-            raise ValueError("%s: pred must be [k,%d,%d], got %s" % (who, self.h, self.w, tuple(pred.shape)))
-        k = int(pred.shape[0])
-        planes = [("pred", pred, (k, self.h, self.w), (torch.float32, torch.uint8)),
-                  ("gt", gt, (k, self.h, self.w), (torch.float32, torch.uint8))]
-        if trimap is not None:
-            planes.append(("trimap", trimap, (k, self.h, self.w), (torch.uint8,)))
+        who, matte, dims = "MatteScorer.add", (torch.float32, torch.uint8), {"h": self.h, "w": self.w}
+        dims["k"] = k = ops.check_array(who, "pred", pred, matte, "k,h,w", ops.EITHER, **dims)[0]
         for name, given, mode in (("backward", backward, "given"), ("cmp", cmp, "estimate")):
             if (given is not None) != (self.flow == mode):
                 raise ValueError("%s: %s goes with flow=%r, and then every chunk needs it (this scorer has flow=%r)" %
                                  (who, name, mode, self.flow))
-        if backward is not None:
-            planes.append(("backward", backward, (k, self.h, self.w, 2), (torch.float32,)))
-        if cmp is not None:
-            planes.append(("cmp", cmp, (k, self.h, self.w, 3), (torch.uint8,)))
-        for name, a, shape, dtypes in planes:
-            dt = _dtype_of(a)
-            if dt is None:
-                raise TypeError("%s: %s must be a numpy array or a torch tensor, got %s" % (who, name, type(a).__name__))
-            if dt not in dtypes:
-                raise TypeError("%s: %s must be %s, got %s" % (who, name, " or ".join(str(d) for d in dtypes), a.dtype))
-            if tuple(a.shape) != shape:
-                raise ValueError("%s: %s must be %s, got %s" % (who, name, list(shape), tuple(a.shape)))
-            if isinstance(a, torch.Tensor):
-                if not a.is_cuda:
-                    raise TypeError("%s: %s is a host tensor; pass a numpy array or a ROCm device tensor" % (who, name))
-                if not a.is_contiguous():
-                    raise ValueError("%s: %s must be contiguous" % (who, name))
-        dts = (_dtype_of(pred), _dtype_of(gt))
+        for name, a, dtypes, shapes in (("gt", gt, matte, "k,h,w"), ("trimap", trimap, (torch.uint8,), "k,h,w"),
+                                        ("backward", backward, (torch.float32,), "k,h,w,2"),
+                                        ("cmp", cmp, (torch.uint8,), "k,h,w,3")):
+            if a is not None or name == "gt":
+                ops.check_array(who, name, a, dtypes, shapes, ops.EITHER, **dims)
+        dts = (ops.torch_dtype(pred), ops.torch_dtype(gt))
         if self._dtypes is not None and dts != self._dtypes:
             raise TypeError("%s: pred / gt were %s / %s so far and are %s / %s now; reset() starts a new clip" %
                             ((who,) + self._dtypes + dts))
@@ -114,7 +77,7 @@ class MatteScorer:
         zeros are not read."""
         o = self.flow_options
         if self._pyr is None:
-            floats = ops.flow_pyramid_floats(self.h, self.w, o["levels"])
+            floats = (ops.flow_pyramid_floats(self.h, self.w, o["levels"]) + 3) // 4 * 4  # row 1 16-byte aligned too
             self._pyr = torch.zeros((2, floats), dtype=torch.float32, device=self.device)
             self._flow_work = torch.zeros(ops.flow_workspace_bytes(self.h, self.w, o["levels"]), dtype=torch.uint8,
                                           device=self.device)

@@ -37,12 +37,14 @@ import numpy as np
 import torch
 
 from . import ops
+from .flow_track import FlowTracker
 from .pipeline import OUT_DTYPES  # noqa: F401  (public)
 from .pipeline import PER_FRAME, Slot, SlotPipeline, check_new_bg, check_out, check_static_bg
 from .split6 import rerun_x6
 
 PROPAGATE = "propagate"
 AUTO = "auto"
+U8 = (torch.uint8,)
 
 
 class _Slot(Slot):
@@ -187,14 +189,12 @@ class FrameStream(SlotPipeline):
         if not self.propagate and (flow is not None or flow_options is not None):
             raise ValueError("FrameStream: flow and flow_options go with trimap=%r" % PROPAGATE)
         self.grow = ops.check_grow("FrameStream", grow)
-        flow = "estimate" if flow is None else flow
-        if flow not in ops.FLOW_MODES:
-            raise ValueError("FrameStream: flow must be one of %s, got %r" % (ops.FLOW_MODES, flow))
-        self.estimate = self.propagate and flow == "estimate"
-        if flow_options is not None and not self.estimate:
-            raise ValueError("FrameStream: flow_options go with flow='estimate'")
+        if self.propagate:  # (flow=None stands for "estimate")
+            flow_options = ops.check_flow_mode("FrameStream", flow, flow_options, h, w, (None,) + ops.FLOW_MODES,
+                                               "estimate")
+        self.estimate = self.propagate and flow_options is not None
         if self.estimate:
-            self.flow_options = ops.flow_options("FrameStream: flow_options", h, w, flow_options)
+            self.flow_options = flow_options
         # gain="fit": the fit's options (None: no gain)
         self.gain = ops.check_gain_mode("FrameStream", gain, gain_options)
         # the plates
@@ -204,7 +204,6 @@ class FrameStream(SlotPipeline):
         self.trimap, self.static_bg, self.out, self.graph = bool(trimap), static_bg, out, bool(graph)
         self.device = model.device
         self.overflowed_chunks = []
-        self._plate = self._new_plate = None
         self._plate_lo = self._guided_work = None  # scale > 1: the reduced plate, the guided filter's workspace
         self._gain_work = self._gain_last = None   # gain="fit": the fit's workspace; the last chunk's (slot, frames)
         self._x6 = None
@@ -231,29 +230,18 @@ class FrameStream(SlotPipeline):
     def _check_frames(self, cmp, bg, tri, nw):
         """The frames of one item: cmp, bg | None, the per-frame trimaps | None, and new_bg with new_bg="per_frame"
         -> (k, new_bg)."""
-        if not isinstance(cmp, np.ndarray):
-            raise TypeError("FrameStream: cmp must be a numpy array, got %s" % type(cmp).__name__)
+        k = ops.check_array("FrameStream", "cmp", cmp, U8, "k,h,w,3", h=self.h, w=self.w)[0]
         if (bg is None) != (self.static_bg is not None):
             raise ValueError("FrameStream: bg is None exactly when a static_bg was given")
         if not (self.propagate or self.auto) and (tri is None) == self.trimap:
             raise ValueError("FrameStream: trimap is None exactly when trimap=False")
-        for name, a in (("bg", bg), ("trimap", tri)):
-            if a is not None and not isinstance(a, np.ndarray):
-                raise TypeError("FrameStream: %s must be a numpy array, got %s" % (name, type(a).__name__))
-        k, _, _, nb = ops._check_u8_frames(cmp, self.static_bg if bg is None else bg, tri)
-        if tuple(cmp.shape[1:3]) != (self.h, self.w):
-            raise ValueError("FrameStream: frames must be %d x %d, got %s" % (self.h, self.w, tuple(cmp.shape)))
-        if bg is not None and nb != k:
-            raise ValueError("FrameStream: bg must be [k,h,w,3] like cmp, got %s" % (tuple(bg.shape),))
+        for name, a, shapes in (("bg", bg, "k,h,w,3"), ("trimap", tri, "k,h,w")):
+            if a is not None:
+                ops.check_array("FrameStream", name, a, U8, shapes, k=k, h=self.h, w=self.w)
         if k > self.chunk:
             raise ValueError("FrameStream: an item of %d frames exceeds chunk=%d" % (k, self.chunk))
         if self.new_bg is PER_FRAME:
-            if not isinstance(nw, np.ndarray):
-                raise TypeError("FrameStream: new_bg must be a numpy array, got %s" % type(nw).__name__)
-            if nw.dtype != np.uint8:
-                raise TypeError("FrameStream: new_bg must be uint8, got %s" % nw.dtype)
-            if nw.shape != cmp.shape:
-                raise ValueError("FrameStream: new_bg must be [k,h,w,3] like cmp, got %s" % (tuple(nw.shape),))
+            ops.check_array("FrameStream", "new_bg", nw, U8, "k,h,w,3", k=k, h=self.h, w=self.w)
         return k, nw
 
     def _check_propagate_item(self, item):
@@ -266,16 +254,11 @@ class FrameStream(SlotPipeline):
             raise ValueError("FrameStream: the first item of a run carries a key trimap")
         if (bw is None) != self.estimate:
             raise ValueError("FrameStream: backward is None exactly when flow='estimate'")
-        for name, a, dt in (("key", key, np.uint8), ("backward", bw, np.float32)):
-            if a is not None and not isinstance(a, np.ndarray):
-                raise TypeError("FrameStream: %s must be a numpy array, got %s" % (name, type(a).__name__))
-            if a is not None and a.dtype != dt:
-                raise TypeError("FrameStream: %s must be %s, got %s" % (name, np.dtype(dt).name, a.dtype))
-        if key is not None and key.shape != (self.h, self.w):
-            raise ValueError("FrameStream: key must be [h,w] = %s, got %s" % ((self.h, self.w), key.shape))
+        if key is not None:
+            ops.check_array("FrameStream", "key", key, U8, "h,w", h=self.h, w=self.w)
         k, nw = self._check_frames(cmp, bg, None, item[4] if per_frame else None)
-        if bw is not None and bw.shape != (k, self.h, self.w, 2):
-            raise ValueError("FrameStream: backward must be [k,h,w,2] = %s, got %s" % ((k, self.h, self.w, 2), bw.shape))
+        if bw is not None:
+            ops.check_array("FrameStream", "backward", bw, (torch.float32,), "k,h,w,2", k=k, h=self.h, w=self.w)
         self._keyed = True
         return cmp, bg, key, k, nw, bw
 
@@ -283,15 +266,12 @@ class FrameStream(SlotPipeline):
     def _setup(self):
         self.model.prepare()
         self._make_streams()
-        if self.static_bg is not None:
-            self._plate = torch.from_numpy(self.static_bg).to(self.device)
+        self._upload_plates()
         if self.scale > 1:  # the plate at the model's size, once; one workspace for every slot, like _auto_work
             if self._plate is not None and self.gain is None:  # (a gained plate is reduced per chunk)
                 self._plate_lo = ops.frames_reduce_u8(self._plate[None], self.scale)
             self._guided_work = torch.zeros(ops.guided_workspace_bytes(self.chunk, self.hm, self.wm), dtype=torch.uint8,
                                             device=self.device)
-        if isinstance(self.new_bg, np.ndarray):
-            self._new_plate = torch.from_numpy(self.new_bg).to(self.device)
         if self.gain is not None:  # one workspace for every slot, like _auto_work
             self._gain_work = torch.zeros(ops.plate_gain_workspace_bytes(self.chunk), dtype=torch.uint8,
                                           device=self.device)
@@ -317,29 +297,20 @@ class FrameStream(SlotPipeline):
     def _setup_propagate(self):
         """What the trimap chain keeps between chunks, once for every slot (the chains run one after another on the
         compute stream) and at fixed addresses (every slot's graphs read and leave it there): the last frame's trimap
-        and, with flow="estimate", the pyramids of the previous chunk's last frame (row 0) and of this chunk's frames."""
+        and, with flow="estimate", the FlowTracker's pyramids of the previous chunk's last frame and of this chunk's."""
         dev, h, w = self.device, self.h, self.w
         self._tri_last = torch.zeros((h, w), dtype=torch.uint8, device=dev)
         self._tri_work = torch.zeros(max(ops.trimap_propagate_workspace_bytes(h, w, self.grow), 1), dtype=torch.uint8,
                                      device=dev)
         if self.estimate:
-            levels = self.flow_options["levels"]
-            floats = (ops.flow_pyramid_floats(h, w, levels) + 3) // 4 * 4  # every row 16-byte aligned
-            self._pyr = torch.zeros((self.chunk + 1, floats), dtype=torch.float32, device=dev)
-            self._flow_work = torch.zeros(ops.flow_workspace_bytes(h, w, levels), dtype=torch.uint8, device=dev)
+            self._flow = FlowTracker(h, w, self.flow_options, dev, frames=self.chunk)
 
     def _trimaps(self, s, k, keyed):
         """The trimaps of the slot's first k frames into s.d_tri, on the current stream: the key or the propagated last
         trimap for frame 0, then frame by frame; with flow="estimate" each frame's pyramid and its flow against the
         previous frame's first.  The last trimap (and pyramid) stay behind for the next chunk."""
         if self.estimate:
-            o, pyr = self.flow_options, self._pyr
-            for j in range(k):
-                ops.flow_pyramid(s.d_cmp[j], o["levels"], out=pyr[j + 1], work=self._flow_work)
-                if j or not keyed:
-                    ops.flow_from_pyramids(pyr[j + 1], pyr[j], self.h, self.w, o["levels"], o["warps"], o["iters"],
-                                           o["alpha"], out=s.d_bw[j], work=self._flow_work)
-            pyr[0].copy_(pyr[k])
+            self._flow.advance(s.d_cmp[:k], s.d_bw[:k], has_previous=not keyed)
         for j in range(k):
             if j == 0 and keyed:
                 s.d_tri[0].copy_(s.d_key[0])
@@ -370,9 +341,7 @@ class FrameStream(SlotPipeline):
     def _background(self, s, k):
         """What the chain of the slot's first k frames takes for the background: the plate, the uploaded per-frame
         backgrounds, or with gain="fit" the slot's gained copy (made by _before)."""
-        if self.gain is not None:
-            return s.g_bg[:k]
-        return self._plate if self._plate is not None else s.d_bg[:k]
+        return s.g_bg[:k] if self.gain is not None else self._plates(s, k)[0]
 
     def _feed(self, s, k, bg):
         """The network input of the slot's first k frames from its uint8 frames; with scale > 1 from their reductions."""
@@ -402,16 +371,14 @@ class FrameStream(SlotPipeline):
 
     def _download(self, s, k):
         """The result of the slot's first k frames from its alpha (and, composed, its uint8 inputs)."""
-        bg = self._background(s, k)
-        nw = self._new_plate if self._new_plate is not None else None if s.d_nw is None else s.d_nw[:k]
-        s.download(s.alpha[:k], s.d_cmp[:k], bg, nw)
+        s.download(s.alpha[:k], s.d_cmp[:k], self._background(s, k), self._plates(s, k)[1])
 
     def _before(self, s, k, keyed):
         """What the chain of the slot's first k frames runs before the forward, on the current stream: with
         gain="fit" the gains and the gained background, with trimap="propagate" or "auto" the frames' trimaps, then the
         ingest."""
         if self.gain is not None:
-            bg = self._plate if self._plate is not None else s.d_bg[:k]
+            bg = self._plates(s, k)[0]
             ops.plate_gain_fit(s.d_cmp[:k], bg, out=s.gain[:k], support=s.support[:k], work=self._gain_work, **self.gain)
             ops.plate_gain_apply(bg, s.gain[:k], out=s.g_bg[:k])
         bg = self._background(s, k)

@@ -83,15 +83,15 @@ class VideoMatter:
         every chunk's frames are made by ops.frames_from_u8 inside that chunk's graph (or eagerly), so ``run()``
         reads the uint8 tensors as they are then: the float64 mean subtraction of the reference's feed
         (loader.py:45,75-78), bit for bit.  Otherwise it is the VideoMatter of those frames."""
-        f, h, w, _ = ops._check_u8_frames(cmp, bg, trimap)
+        f, h, w, _ = ops._check_frames_and_bg("from_uint8", cmp, bg)
+        if trimap is not None:
+            ops._check_tensor("from_uint8", "trimap", trimap, (torch.uint8,), "n,h,w", n=f, h=h, w=w)
         c = 6 if trimap is None else 7
         if c != model.IN_CH:
             raise ValueError("%s takes %d input channels: trimap %s" % (type(model).__name__, model.IN_CH,
                                                                        "required" if model.IN_CH == 7 else "not taken"))
         for t in (cmp, bg) + (() if trimap is None else (trimap,)):
             ops._require_gpu(t)
-            if not t.is_contiguous():
-                raise ValueError("from_uint8: contiguous uint8 tensors expected")
         return cls(model, ops.frame_buffer(model, f, h, w), chunk, graph, alpha, _u8=(cmp, bg, trimap))
 
     def _ingest(self, k):
