@@ -970,6 +970,49 @@ int vm_plate_gain_fit(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int 
                       int32_t* gain, int32_t* support, void* work, void* stream);
 int vm_plate_gain_apply(const uint8_t* bg, int nb, const int32_t* gain, int n, int h, int w, uint8_t* out, void* stream);
 
+/* ---------------------------------------------------------------- flow-compensated temporal matte filter
+ * A model that mattes every frame on its own leaves mattes that shimmer along soft edges (vm_matte_score's dtSSD and
+ * MESSDdt measure it).  This is a post-filter on the model's output: frame j's matte is pulled towards the previous
+ * *filtered* matte, sampled where the backward flow says the pixel came from, and two gates close the pull where it would
+ * smear a real change (the reference has no counterpart).  All f32, one operation per step, nothing contracted.  Frame j
+ * has alpha[j] (the model's matte), cmp[j], backward[j] (frame j at (x, y) ~ frame j - 1 at (x + u, y + v), (u, v) =
+ * backward[j,y,x]), the previous filtered matte s' and the previous frame cmp'.  With unit(v) = vm_matte_score's clamp to
+ * [0,1] (NaN -> 0), per pixel (x, y):
+ *   a        unit(alpha[j,y,x])
+ *   target   xs = (float)x + u, ys = (float)y + v;  inside = 0 <= xs <= w - 1 and 0 <= ys <= h - 1 (false for NaN);
+ *            outside, the target is (0, 0)
+ *   taps     x0 = floor(xs), x1 = min(x0 + 1, w - 1), fx = xs - x0, and the same in y: vm_matte_score's bilinear
+ *            convention;  sample(v) = top + fy (bot - top), top = v00 + fx (v01 - v00), bot = v10 + fx (v11 - v10)
+ *   p        sample(unit(s'))  (s' is a filtered matte, which unit leaves as it is; a caller's prev_alpha is clamped)
+ *   d        max over the 3 channels of |(float)cmp[j,y,x,ch] - sample((float)cmp'[...,ch])|
+ *   k        unit(1 - d inv_tol) * unit(1 - |a - p| inv_jump), and 0 where not inside;  inv_tol = 1.0f / tol and
+ *            inv_jump = 1.0f / jump, divided once on the host in f32
+ *   out      s = unit(a + (strength k) (p - a))
+ *   weight   k
+ * A frame with nothing before it (frame 0 without prev_*) gets s = a and weight 0.  The n frames are processed in
+ * order, one launch each (csrc/matte_smooth.hip): frame 0 reads (prev_alpha, prev_cmp), frame j >= 1 reads (out[j - 1],
+ * cmp[j - 1]); backward[0] is not read without a predecessor.
+ *   alpha    f32 [n,h,w];  cmp uint8 [n,h,w,3];  backward f32 [n,h,w,2] (reader.read_flow layout)
+ *   prev_alpha, prev_cmp   f32 [h,w], uint8 [h,w,3]: the frame before frame 0; both NULL: there is none
+ *   strength 0 <= strength < 1: the share of the previous matte where both gates are open
+ *   tol      > 0, finite, in grey levels: the colour difference at which the photometric gate is shut
+ *   jump     > 0, finite, in matte units: the matte difference at which the jump gate is shut
+ *   out      f32 [n,h,w]; may be exactly `alpha` (in place: a thread reads only its own pixel of alpha[j])
+ *   weight   f32 [n,h,w] or NULL: where the filter held back
+ * What this is not: it is one-sided and recursive - one frame of history, no look-ahead, so it lags rather than centres;
+ * it detects no cuts (a cut is only caught by the photometric gate, pixel by pixel); the gate is colour-based, so a
+ * flicker where subject and background share a colour passes through it, and a wrong flow between equal colours smears;
+ * it is no substitute for a recurrent model.  Its effect was measured on a synthetic clip only (tests/matte_smooth_ref.py,
+ * DESIGN 3.4n): nothing is known about a trained model's mattes on real footage, and the defaults are untuned.
+ * cmp and prev_cmp may sit at any byte address; the f32 arrays are 4-byte aligned.  No workspace, no allocation, no
+ * synchronisation: the call can be captured in a graph.  VM_EINVAL for a NULL alpha / cmp / backward / out, exactly one
+ * of prev_alpha / prev_cmp, n, h or w < 1, n * h * w * 3 beyond 2^31 - 1, strength, tol or jump out of range (NaN
+ * included), a misaligned f32 pointer, out overlapping an input other than being alpha itself, or weight overlapping
+ * an input or out (checked before any HIP call). */
+int vm_matte_smooth(const float* alpha, const uint8_t* cmp, const float* backward, const float* prev_alpha,
+                    const uint8_t* prev_cmp, int n, int h, int w, float strength, float tol, float jump, float* out,
+                    float* weight, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

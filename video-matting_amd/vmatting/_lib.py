@@ -223,6 +223,8 @@ SIGNATURES = [
     ("vm_plate_gain_fit", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
     ("vm_plate_gain_apply", c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("vm_matte_smooth", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
+                                c_float, c_void_p, c_void_p, c_void_p]),
 ]
 
 _lib = None

@@ -1627,6 +1627,88 @@ def plate_gain_apply(bg, gain, out=None):
     return out
 
 
+# ---------------------------------------------------------------- flow-compensated temporal matte filter
+
+# the share of the previous matte, the colour difference (grey levels) and the matte difference at which the gates shut:
+# the values of the CPU prototype on a synthetic clip, untuned on real footage
+SMOOTH_DEFAULTS = {"strength": 0.5, "tol": 24.0, "jump": 0.3}
+SMOOTH_FLOW = "flow"
+_F32_MAX = float(np.finfo(np.float32).max)
+
+
+def check_smooth_options(who, strength=SMOOTH_DEFAULTS["strength"], tol=SMOOTH_DEFAULTS["tol"],
+                         jump=SMOOTH_DEFAULTS["jump"]):
+    """The options of vm_matte_smooth as it checks them, on the host: numbers (no bool), 0 <= strength < 1, tol and jump
+    positive and finite as f32 -> (strength, tol, jump) as floats."""
+    vals = []
+    for name, v in (("strength", strength), ("tol", tol), ("jump", jump)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError("%s: %s must be a number, got %r" % (who, name, v))
+        vals.append(float(v))
+    strength, tol, jump = vals  # (the library sees them rounded to f32, and checks again)
+    if not 0.0 <= strength < 1.0:
+        raise ValueError("%s: strength must be in [0, 1), got %r" % (who, strength))
+    for name, v in (("tol", tol), ("jump", jump)):
+        if not 0.0 < v <= _F32_MAX:
+            raise ValueError("%s: %s must be a positive finite number, got %r" % (who, name, v))
+    return strength, tol, jump
+
+
+def smooth_options(who, options):
+    """A dict over SMOOTH_DEFAULTS (None: the defaults), checked -> {"strength": ..., "tol": ..., "jump": ...}."""
+    return _options(who, SMOOTH_DEFAULTS, options, check_smooth_options)
+
+
+def check_smooth_mode(who, smooth, options):
+    """The ``smooth`` argument of FrameStream: None or "flow", and its ``smooth_options`` (a dict over SMOOTH_DEFAULTS)
+    only with "flow" -> the checked options, or None without the filter."""
+    if smooth is not None and not (isinstance(smooth, str) and smooth == SMOOTH_FLOW):
+        raise ValueError("%s: smooth must be None or %r, got %r" % (who, SMOOTH_FLOW, smooth))
+    if smooth is None:
+        if options is not None:
+            raise ValueError("%s: smooth_options go with smooth=%r" % (who, SMOOTH_FLOW))
+        return None
+    return smooth_options("%s: smooth_options" % who, options)
+
+
+def matte_smooth(alpha, cmp, backward, prev=None, strength=SMOOTH_DEFAULTS["strength"], tol=SMOOTH_DEFAULTS["tol"],
+                 jump=SMOOTH_DEFAULTS["jump"], out=None, weight=None):
+    """vm_matte_smooth: the mattes of consecutive frames filtered along the flow.  alpha f32 [n,h,w] or [n,h,w,1] (the
+    model's mattes), cmp u8 [n,h,w,3] BGR, backward f32 [n,h,w,2] (frame j's flow into frame j - 1, reader.read_flow
+    layout, as estimate_flow returns it) -> f32 of alpha's shape: frame j's matte pulled towards the previous filtered
+    matte at the flow's target by ``strength`` times a weight that is 1 where the frame equals the warped previous
+    frame and the matte the warped previous matte, and falls to 0 at a colour difference of ``tol`` grey levels or a
+    matte difference of ``jump`` (include/vmatting.h).  ``prev`` = (prev_alpha f32 [h,w] or [h,w,1], prev_cmp u8
+    [h,w,3]): the filtered matte and the frame before frame 0; None: frame 0 starts a run, its result is its clamped
+    matte and backward[0] is not read.  ``out``: a contiguous f32 device tensor of alpha's shape, which may be
+    ``alpha`` itself (in place); ``weight``: one more, which receives the weights (0 where the filter held back
+    entirely).  out is allocated when None."""
+    who = "matte_smooth"
+    shape = _check_tensor(who, "alpha", alpha, (torch.float32,), "n,h,w | n,h,w,1")
+    n, h, w = shape[:3]
+    dims = {"n": n, "h": h, "w": w}
+    _check_tensor(who, "cmp", cmp, (torch.uint8,), "n,h,w,3", **dims)
+    _check_tensor(who, "backward", backward, (torch.float32,), "n,h,w,2", **dims)
+    pa = pc = None
+    if prev is not None:
+        if not isinstance(prev, (tuple, list)) or len(prev) != 2:
+            raise TypeError("%s: prev must be the pair (prev_alpha, prev_cmp)" % who)
+        pa, pc = prev
+        _check_tensor(who, "prev_alpha", pa, (torch.float32,), "h,w | h,w,1", **dims)
+        _check_tensor(who, "prev_cmp", pc, (torch.uint8,), "h,w,3", **dims)
+    strength, tol, jump = check_smooth_options(who, strength, tol, jump)
+    out = _out_or_new(who, "out", out, torch.float32, "n,h,w,1 | n,h,w" if len(shape) == 4 else "n,h,w | n,h,w,1",
+                      alpha.device, ValueError, **dims)
+    if weight is not None:
+        _check_tensor(who, "weight", weight, (torch.float32,), "n,h,w | n,h,w,1", ValueError, **dims)
+    for t in (alpha, cmp, backward, pa, pc, out, weight):
+        if t is not None:
+            _require_gpu(t)
+    check(lib().vm_matte_smooth(_ptr(alpha), _ptr(cmp), _ptr(backward), _ptr(pa), _ptr(pc), n, h, w, strength, tol, jump,
+                                _ptr(out), _ptr(weight), stream_handle()), who)
+    return out
+
+
 # ---------------------------------------------------------------- training step (train.py:288-343, config 5)
 
 def matting_loss_backward(pred, gt, raw_fg, in_bg, in_cmp, out=None):

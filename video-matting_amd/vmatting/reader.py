@@ -181,6 +181,39 @@ def match_plate(cmp_u8, bg_u8, **options):
     return plate, gain.astype(np.float32) / np.float32(ops.GAIN_ONE), support.astype(np.int64)
 
 
+def smooth_mattes(mattes, frames_u8, flows=None, **options):
+    """The mattes of a clip filtered along time: what FrameStream(smooth="flow") does to the model's output, on a clip
+    in host memory.  mattes f32 (clamped to [0,1]) or uint8 (q / 255) [n,h,w], the clip's frames uint8 [n,h,w,3] BGR,
+    ``flows`` f32 [n,h,w,2]: frame j's backward flow into frame j - 1 in read_flow layout (entry 0 is not read), or None
+    to estimate them from consecutive frames (ops.estimate_flow at its defaults; h and w at least 16); ``options`` over
+    ops.SMOOTH_DEFAULTS (strength, tol, jump) -> f32 [n,h,w]: frame 0 as it is, every later matte pulled towards the
+    filtered matte before it along the flow, gated by the frames' colours and the matte's jump (ops.matte_smooth,
+    include/vmatting.h).  One frame of history, no look-ahead, no cut detection.  numpy in, numpy out, through the
+    kernels."""
+    from vmatting import ops
+    who = "smooth_mattes"
+    opts = ops.smooth_options(who, options)
+    mattes, frames_u8 = np.asarray(mattes), np.asarray(frames_u8)
+    n, h, w = ops.check_array(who, "mattes", mattes, (torch.float32, torch.uint8), "n,h,w")
+    ops.check_array(who, "frames", frames_u8, U8, "n,h,w,3", n=n, h=h, w=w)
+    if flows is None:
+        ops.check_flow_options(who, h, w)
+    else:
+        flows = np.asarray(flows)
+        ops.check_array(who, "flows", flows, (torch.float32,), "n,h,w,2", n=n, h=h, w=w)
+    if mattes.dtype == np.uint8:
+        mattes = mattes.astype(np.float32) / np.float32(255.0)
+    alpha, cmp = _stack(mattes, False), _stack(frames_u8, False)
+    if flows is None:
+        backward = torch.zeros((n, h, w, 2), dtype=torch.float32, device=cmp.device)
+        work = torch.empty(ops.flow_workspace_bytes(h, w), dtype=torch.uint8, device=cmp.device)
+        for j in range(1, n):
+            ops.estimate_flow(cmp[j], cmp[j - 1], out=backward[j], work=work)
+    else:
+        backward = _stack(flows, False)
+    return ops.matte_smooth(alpha, cmp, backward, out=alpha, **opts).cpu().numpy()
+
+
 def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, fill=None, gain=None,
                       gain_options=None):
     """The trimap of a frame from its difference to the background plate: what FrameStream(trimap="auto") feeds the

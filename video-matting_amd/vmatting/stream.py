@@ -30,6 +30,12 @@ frames (and per-frame backgrounds and trimaps) by ``scale`` (ops.frames_reduce_u
 frames, and carries its matte back to the frames' size with a guided filter steered by the full-resolution frame
 (ops.guided_coeffs, ops.guided_apply); the download then works on full-resolution data as ever.
 
+``smooth="flow"``: mattes made frame by frame shimmer along soft edges.  The chunk's chain then ends, before the
+download, with ops.matte_smooth in place on the full-resolution alpha: every matte is pulled towards the previous
+filtered matte along the frames' backward flow, gated by the frames' colours and the matte's jump.  It is a filter on
+the model's output, so the forward stays chunked; the last filtered matte and the last frame stay on the device for the
+next chunk.
+
 This is one process's share of a clip; sharding a clip across ranks stays video.shard's job.
 """
 
@@ -64,13 +70,14 @@ class _Slot(Slot):
                          n, h, w, fs.out, flag=fs.model.split_mode == "f16x3")  # f16x3: this slot's range flag
         if fs.propagate or fs.auto:  # the chunk's trimaps are made on the device: no pinned twin, nothing uploaded
             self.d_tri = torch.zeros((n, h, w), dtype=u8, device=fs.device)
-            if fs.estimate:
-                self.d_bw = torch.zeros((n, h, w, 2), dtype=torch.float32, device=fs.device)
+        if fs.estimate:  # ... and so are its flows (trimap="propagate" and smooth="flow" share them)
+            self.d_bw = torch.zeros((n, h, w, 2), dtype=torch.float32, device=fs.device)
         if fs.gain is not None:  # the chunk's background under its frames' gains, the gains and their support
             self.g_bg = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device)
             self.gain = torch.zeros((n, 3), dtype=torch.int32, device=fs.device)
             self.support = torch.zeros((n, 3), dtype=torch.int32, device=fs.device)
-        self.graphs = {}  # trimap="propagate": the full-chunk graph of a keyed item (True) and of a continued one
+        self.graphs = {}  # trimap="propagate" / smooth="flow": the full-chunk graph of an item that restarts the
+        #                   chain's state (True: a keyed item, the first item of a run) and of one that continues
         if fs.scale > 1:
             # the model's side of the chunk: the reduced uint8 frames it is fed from, its matte, and the guided
             # filter's coefficients; the frame buffer below is then the model's size too
@@ -150,12 +157,33 @@ class FrameStream(SlotPipeline):
     it, and below h w / min_share the gain is 1; the new plate of out="over" is not gained.  gain=None is the stream
     without any of this, call for call.  ClipStream, VideoMatter and PlateEstimator do not take it.
 
+    ``smooth`` (None, the default, or "flow"): filter the mattes along time before they are quantised or composed.
+    After the forward (and, with ``scale``, the upsampling) frame j's matte is pulled towards the filtered matte of
+    frame j - 1, sampled where frame j's backward flow says each pixel came from, by ``strength`` times a weight that
+    is 1 where frame j equals the warped frame j - 1 and the matte the warped previous matte, and falls to 0 at a
+    colour difference of ``tol`` grey levels or a matte difference of ``jump`` (ops.matte_smooth, include/vmatting.h;
+    ``smooth_options`` a dict over ops.SMOOTH_DEFAULTS: strength, tol, jump - the values of a CPU prototype, untuned on
+    real footage).  The recurrence runs across chunks: the last filtered matte and the last frame stay on the device.
+    It restarts (the frame has no predecessor and keeps its matte) at the first item of a run and, with
+    trimap="propagate", at every keyed item.  The flows are those of trimap="propagate" where that is on, estimated or
+    given; otherwise they are estimated from consecutive frames (``flow`` None or "estimate", ``flow_options``; h and
+    w at least 16), which costs one flow estimate per frame.  It works on the full-resolution matte with every ``out``,
+    trimap mode, ``scale`` and ``gain``; the result is ops.matte_smooth run over the whole clip on the unsmoothed
+    stream's "f32" mattes, bit for bit; reader.smooth_mattes does that to a clip in host memory.  ``last_weight()``
+    returns the weights of the last frame after a run: 0 is where the filter held back.  What it is not: one-sided and
+    recursive - one frame of history, no look-ahead; it detects no cuts (a cut is caught only by the colour gate,
+    pixel by pixel); the gate is colour-based, so a flicker where subject and plate share a colour passes through;
+    its effect is measured on a synthetic clip only, not on a trained model's mattes of real footage.  A
+    model whose split_mode is "f16x3" is refused: an overflowed chunk is run again when it is retired, after the next
+    chunk has consumed its last matte, so the recurrence could not be repaired.  smooth=None is the stream without any
+    of this, call for call.  ClipStream and VideoMatter do not take it.
+
     If the source raises, or yields a wrong shape, dtype or k, the chunks already taken are finished and yielded, the
     streams are synchronised, and the exception then propagates; the object can run again."""
 
     def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True, new_bg=None,
                  flow=None, flow_options=None, grow=1, auto_options=None, auto_fill=None, scale=1, guided_options=None,
-                 gain=None, gain_options=None):
+                 gain=None, gain_options=None, smooth=None, smooth_options=None):
         h, w, chunk, depth = int(h), int(w), int(chunk), int(depth)
         if h < 1 or w < 1 or chunk < 1 or depth < 1:
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
@@ -185,14 +213,22 @@ class FrameStream(SlotPipeline):
         if auto_fill is not None and not self.auto:
             raise ValueError("FrameStream: auto_fill goes with trimap=%r" % AUTO)
         self.auto_fill = ops.check_fill("FrameStream: auto_fill", auto_fill)
-        # trimap="propagate": the unknown band's growth, and where the flows come from
-        if not self.propagate and (flow is not None or flow_options is not None):
-            raise ValueError("FrameStream: flow and flow_options go with trimap=%r" % PROPAGATE)
+        # smooth="flow": the filter's options (None: no filter)
+        self.smooth = ops.check_smooth_mode("FrameStream", smooth, smooth_options)
+        if self.smooth is not None and model.split_mode == "f16x3":
+            raise ValueError("FrameStream: smooth=%r does not go with an f16x3 model: an overflowed chunk is run again "
+                             "after the next chunk has consumed its last matte" % ops.SMOOTH_FLOW)
+        # trimap="propagate": the unknown band's growth; with it or smooth="flow": where the flows come from
+        flows = self.propagate or self.smooth is not None
+        if not flows and (flow is not None or flow_options is not None):
+            raise ValueError("FrameStream: flow and flow_options go with trimap=%r or smooth=%r" %
+                             (PROPAGATE, ops.SMOOTH_FLOW))
         self.grow = ops.check_grow("FrameStream", grow)
-        if self.propagate:  # (flow=None stands for "estimate")
-            flow_options = ops.check_flow_mode("FrameStream", flow, flow_options, h, w, (None,) + ops.FLOW_MODES,
+        if flows:  # (flow=None stands for "estimate"; only the propagation's items carry given flows)
+            flow_options = ops.check_flow_mode("FrameStream", flow, flow_options, h, w,
+                                               (None,) + ops.FLOW_MODES if self.propagate else (None, "estimate"),
                                                "estimate")
-        self.estimate = self.propagate and flow_options is not None
+        self.estimate = flows and flow_options is not None
         if self.estimate:
             self.flow_options = flow_options
         # gain="fit": the fit's options (None: no gain)
@@ -209,6 +245,9 @@ class FrameStream(SlotPipeline):
         self._x6 = None
         self._keyed = False      # trimap="propagate": whether this run has had its first key
         self._tri_last = None    # ... and the last frame's trimap, at a fixed device address
+        self._started = False    # whether this run has had its first item (smooth="flow" restarts there)
+        self._smooth_last = self._smooth_cmp = self._smooth_weight = None  # smooth="flow": what _setup_smooth keeps
+        self._smooth_k = 0       # ... and the frames of the last chunk submitted
 
     # ------------------------------------------------------------------ checks (host only)
     def check_item(self, item):
@@ -275,8 +314,12 @@ class FrameStream(SlotPipeline):
         if self.gain is not None:  # one workspace for every slot, like _auto_work
             self._gain_work = torch.zeros(ops.plate_gain_workspace_bytes(self.chunk), dtype=torch.uint8,
                                           device=self.device)
+        if self.estimate:  # the pyramids of the previous chunk's last frame and of this chunk's, once for every slot
+            self._flow = FlowTracker(self.h, self.w, self.flow_options, self.device, frames=self.chunk)
         if self.propagate:
             self._setup_propagate()
+        if self.smooth is not None:
+            self._setup_smooth()
         if self.auto:  # one workspace for every slot: the chains run one after another on the compute stream
             self._auto_work = torch.zeros(ops.trimap_from_plate_workspace_bytes(self.chunk, self.h, self.w),
                                           dtype=torch.uint8, device=self.device)
@@ -285,9 +328,10 @@ class FrameStream(SlotPipeline):
                                               dtype=torch.uint8, device=self.device)
         self._slots = [_Slot(self) for _ in range(self.depth)]
         torch.cuda.synchronize(self.device)  # the plates and the zeroed pad channels, before another stream reads them
-        if self.propagate and self.graph:
+        if self._stateful and self.graph:
             # captured here, not with the first full chunk: a capture runs its chain once to warm up, and that run
-            # would move the chain's state (the last trimap, the last pyramid) one chunk ahead of the clip
+            # would move the chain's state (the last trimap, the last pyramid, the last filtered matte) one chunk ahead
+            # of the clip
             with torch.cuda.stream(self._compute):
                 for s in self._slots:
                     for keyed in (True, False):
@@ -296,21 +340,37 @@ class FrameStream(SlotPipeline):
 
     def _setup_propagate(self):
         """What the trimap chain keeps between chunks, once for every slot (the chains run one after another on the
-        compute stream) and at fixed addresses (every slot's graphs read and leave it there): the last frame's trimap
-        and, with flow="estimate", the FlowTracker's pyramids of the previous chunk's last frame and of this chunk's."""
+        compute stream) and at fixed addresses (every slot's graphs read and leave it there): the last frame's
+        trimap."""
         dev, h, w = self.device, self.h, self.w
         self._tri_last = torch.zeros((h, w), dtype=torch.uint8, device=dev)
         self._tri_work = torch.zeros(max(ops.trimap_propagate_workspace_bytes(h, w, self.grow), 1), dtype=torch.uint8,
                                      device=dev)
+
+    def _setup_smooth(self):
+        """What the temporal filter keeps between chunks, once for every slot and at fixed addresses like the trimap
+        chain's state: the last filtered matte and the last frame; and the weights of the chunk in flight (one buffer:
+        the filter writes them in the launches it makes anyway)."""
+        dev, h, w = self.device, self.h, self.w
+        self._smooth_last = torch.zeros((h, w, 1), dtype=torch.float32, device=dev)
+        self._smooth_cmp = torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
+        self._smooth_weight = torch.zeros((self.chunk, h, w, 1), dtype=torch.float32, device=dev)
+
+    @property
+    def _stateful(self):
+        """Whether the chain keeps state between chunks: a slot then has two graphs, graphs[restart]."""
+        return self.propagate or self.smooth is not None
+
+    def _flows(self, s, k, keyed):
+        """flow="estimate": the backward flows of the slot's first k frames into s.d_bw, on the current stream: each
+        frame's pyramid, then its flow against the previous frame's (none for frame 0 of an item that restarts).  Once
+        per chunk, for the trimap chain and the temporal filter alike; the last pyramid stays behind."""
         if self.estimate:
-            self._flow = FlowTracker(h, w, self.flow_options, dev, frames=self.chunk)
+            self._flow.advance(s.d_cmp[:k], s.d_bw[:k], has_previous=not keyed)
 
     def _trimaps(self, s, k, keyed):
         """The trimaps of the slot's first k frames into s.d_tri, on the current stream: the key or the propagated last
-        trimap for frame 0, then frame by frame; with flow="estimate" each frame's pyramid and its flow against the
-        previous frame's first.  The last trimap (and pyramid) stay behind for the next chunk."""
-        if self.estimate:
-            self._flow.advance(s.d_cmp[:k], s.d_bw[:k], has_previous=not keyed)
+        trimap for frame 0, then frame by frame along s.d_bw.  The last trimap stays behind for the next chunk."""
         for j in range(k):
             if j == 0 and keyed:
                 s.d_tri[0].copy_(s.d_key[0])
@@ -326,6 +386,25 @@ class FrameStream(SlotPipeline):
         if self._tri_last is None:
             raise RuntimeError("FrameStream: last_trimap() before any frame was submitted")
         return self._tri_last.cpu().numpy()
+
+    def _smooth(self, s, k, keyed):
+        """smooth="flow": the slot's first k full-resolution mattes filtered in place along s.d_bw, frame 0 against
+        the last filtered matte and frame unless the item restarts; the last of both stay behind for the next chunk."""
+        if self.smooth is not None:
+            prev = None if keyed else (self._smooth_last, self._smooth_cmp)
+            ops.matte_smooth(s.alpha[:k], s.d_cmp[:k], s.d_bw[:k], prev, out=s.alpha[:k],
+                             weight=self._smooth_weight[:k], **self.smooth)
+            self._smooth_last.copy_(s.alpha[k - 1])
+            self._smooth_cmp.copy_(s.d_cmp[k - 1])
+
+    def last_weight(self):
+        """smooth="flow": the f32 [h,w] weights of the last frame submitted, once the run has drained: 1 where the
+        filter took ``strength`` of the previous matte, 0 where it held back (or the frame had no predecessor)."""
+        if self.smooth is None:
+            raise ValueError("FrameStream: last_weight() goes with smooth='flow'")
+        if not self._smooth_k:
+            raise RuntimeError("FrameStream: last_weight() before any frame was submitted")
+        return self._smooth_weight[self._smooth_k - 1, :, :, 0].cpu().numpy()
 
     def last_gains(self):
         """gain="fit": (gains f32 [k,3] = Q12 gain / 4096, support int [k,3]) of the last chunk submitted, once the run
@@ -375,13 +454,14 @@ class FrameStream(SlotPipeline):
 
     def _before(self, s, k, keyed):
         """What the chain of the slot's first k frames runs before the forward, on the current stream: with
-        gain="fit" the gains and the gained background, with trimap="propagate" or "auto" the frames' trimaps, then the
-        ingest."""
+        gain="fit" the gains and the gained background, with flow="estimate" the frames' flows, with
+        trimap="propagate" or "auto" their trimaps, then the ingest.  ``keyed``: the item restarts the chain's state."""
         if self.gain is not None:
             bg = self._plates(s, k)[0]
             ops.plate_gain_fit(s.d_cmp[:k], bg, out=s.gain[:k], support=s.support[:k], work=self._gain_work, **self.gain)
             ops.plate_gain_apply(bg, s.gain[:k], out=s.g_bg[:k])
         bg = self._background(s, k)
+        self._flows(s, k, keyed)
         if self.propagate:
             self._trimaps(s, k, keyed)
         if self.auto:
@@ -390,26 +470,28 @@ class FrameStream(SlotPipeline):
                 ops.trimap_fill_enclosed(s.d_tri[:k], self.auto_fill, out=s.d_tri[:k], work=self._fill_work)
         self._feed(s, k, bg)
 
-    def _after(self, s, k):
-        """... and after it: the matte to full resolution (scale > 1), then quantise | compose -> download."""
+    def _after(self, s, k, keyed=False):
+        """... and after it: the matte to full resolution (scale > 1), the temporal filter (smooth="flow"), then
+        quantise | compose -> download."""
         self._upsample(s, k)
+        self._smooth(s, k, keyed)
         self._download(s, k)
 
     def _chain(self, s, k, keyed=False):
         """Ingest -> forward -> quantise | compose -> download of the slot's first k frames, on the current stream."""
         self._before(s, k, keyed)
         self.model.forward(s.frames[:k], out=self._matte(s, k), overflow=s.flag)
-        self._after(s, k)
+        self._after(s, k, keyed)
 
     def _capture(self, s, keyed=False):
         """The full-chunk chain of one slot as one HIP graph: UNet.capture records the forward over the slot's static
         buffers with _before ahead of it and _after behind it, all on the capturing stream; a leading slice of full
-        length is the buffer itself, so these are _chain's calls.  ``keyed`` (trimap="propagate"): the graph of an item
-        with a key, or of one that continues."""
+        length is the buffer itself, so these are _chain's calls.  ``keyed`` (a chain with state): the graph of an item
+        that restarts it, or of one that continues."""
         n = self.chunk
         graph = self.model.capture(s.frames, static=True, out=self._matte(s, n), overflow=s.flag,
-                                   pre=lambda: self._before(s, n, keyed), post=lambda: self._after(s, n))
-        if self.propagate:
+                                   pre=lambda: self._before(s, n, keyed), post=lambda: self._after(s, n, keyed))
+        if self._stateful:
             s.graphs[keyed] = graph
         else:
             s.graph = graph
@@ -418,7 +500,9 @@ class FrameStream(SlotPipeline):
         s.k, s.index = k, index
         if self.gain is not None:
             self._gain_last = (s, k)
-        keyed = self.propagate and tri is not None
+        # the item restarts the chain's state: it carries a key, or without trimap="propagate" it is a run's first
+        keyed = tri is not None if self.propagate else self.smooth is not None and not self._started
+        self._started, self._smooth_k = True, k
         for name, a in (("cmp", cmp), ("bg", bg), ("key" if self.propagate else "tri", tri), ("bw", bw), ("nw", nw)):
             s.stage(name, a, 1 if name == "key" else k)
         with torch.cuda.stream(self._upload):
@@ -427,7 +511,7 @@ class FrameStream(SlotPipeline):
         with torch.cuda.stream(self._compute):
             self._compute.wait_event(s.uploaded)
             if self.graph and k == self.chunk:
-                if self.propagate:
+                if self._stateful:
                     s.graphs[keyed].replay()
                 else:
                     if s.graph is None:
@@ -454,5 +538,5 @@ class FrameStream(SlotPipeline):
         """Generator: one [k,h,w] matte (numpy, the ``out`` dtype), or one composed [k,h,w,3 | 4] uint8 array, per source
         item, in source order."""
         self.overflowed_chunks = []
-        self._keyed = False
+        self._keyed = self._started = False
         yield from super().run(source)
