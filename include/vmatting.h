@@ -970,6 +970,63 @@ int vm_plate_gain_fit(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int 
                       int32_t* gain, int32_t* support, void* work, void* stream);
 int vm_plate_gain_apply(const uint8_t* bg, int nb, const int32_t* gain, int n, int h, int w, uint8_t* out, void* stream);
 
+/* ---------------------------------------------------------------- the plate's position matched to the frame
+ * Everything driven by the background takes the plate and the frame to be registered pixel for pixel; a bumped tripod, a
+ * handheld plate, lens breathing or a slow pan move the plate by a fraction of a pixel up to a few pixels, and on a textured
+ * background half a pixel is enough to switch the plate trimap off.  One affine map and one photometric gain per frame
+ * are fitted between the grey pyramids (vm_flow_pyramid) of the frame and of the plate, and the plate is resampled through
+ * the map (the reference has no counterpart).  Per frame i:
+ *   cmp_pyr  f32: frame i's pyramid starts at cmp_pyr + i cmp_stride (floats; at least vm_flow_pyramid_bytes / 4);
+ *            bg_pyr likewise with bg_stride, nb == n or nb == 1 (one plate pyramid for all frames; bg_stride is not read);
+ *            both of [h,w] frames at `levels`, levels k = 0 .. K of h_k x w_k pixels, I_k and P_k
+ *   model    p0..p5 and g, deviations from the identity in centred level-0 pixels xc = x - (w - 1) / 2, yc = y - (h - 1) / 2:
+ *            frame pixel (x, y) sees the plate at X = x + ((p0 xc + p1 yc) + p2), Y = y + ((p3 xc + p4 yc) + p5), and
+ *            grey(frame) ~ g grey(plate there).  g is a nuisance parameter that lets the fit work on a frame shot at another
+ *            exposure: it is reported and never applied (vm_plate_gain_fit does that per channel afterwards)
+ *   start    p = 0; g = f32(sum I_K / sum P_K) (f64 sums and quotient) if sum P_K > 0, else 1
+ *   step     `iters` times per level, from K down to 0, all per-pixel terms f32, nothing contracted.  For level pixel (x, y),
+ *            s = 2^k: X0 = (x + 0.5f) s - 0.5f, Y0 likewise, xc = X0 - (w - 1) 0.5f, yc = Y0 - (h - 1) 0.5f, (X, Y) as above
+ *            from (X0, Y0), level position xl = (X + 0.5f) / s - 0.5f, yl likewise;  inside = 0 <= xl <= w_k - 1 and
+ *            0 <= yl <= h_k - 1;  B = vm_flow_estimate's bilinear of P_k (coordinates clamped): Pw = B(xl, yl),
+ *            Gx = ((B(xl + 1, yl) - B(xl - 1, yl)) 0.5f) / s, Gy likewise;  r = I_k - g Pw;  a = g Gx, b = g Gy;
+ *            J = (a xc, a yc, a, b xc, b yc, b, Pw);  inlier = inside and |r| <= tol;  close = inside and |r| <= tol 0.25f
+ *   sums     over the inliers, f64, each term one f32 product widened: the 28 J_u J_v (u <= v), the 7 J_u r; count of the
+ *            inliers, and of the close pixels
+ *   solve    if count min_share >= h_k w_k: (J^T J) d = J^T r by Gaussian elimination without pivoting in f64; a pivot that
+ *            is not positive ends it.  Solved: p_u = f32(f64(p_u) + d_u), g likewise.  Otherwise the step changes nothing
+ *   support  int32 [n]: the close count of the last step, or 0 where that step met a pivot that is not positive (a plate
+ *            without texture has nothing to fit).  The close pixels and not the inliers: two unrelated images leave 33 - 48 %
+ *            of their pixels within 16 grey levels but only about 10 % within 4, a fitted background nearly all of its own
+ *   result   params f32 [n,8] = (p0..p5, g, 0); the identity (0 .. 0, 1, 0) instead if support min_share < h w, if a
+ *            parameter is not finite, or if one of the frame's four corners (-+ (w - 1) / 2, -+ (h - 1) / 2) is displaced by
+ *            more than f32(min(h, w)) / f32(reach) pixels (dx dx + dy dy <= lim lim must hold).  The corner limit guards
+ *            against a diverged fit; it does not promise that every divergence ends outside it
+ *   apply    out uint8 [n,h,w,3]: per pixel (X, Y) as above with (X0, Y0) = (x, y); out = clamp(rint(B(bg[i or 0]))) per
+ *            channel on the bytes as f32, coordinates clamped to the plate (replicate border).  Identity parameters
+ *            reproduce the plate byte for byte
+ * What this is not: one global affine map per frame - no parallax, no rolling shutter, no lens distortion; a textureless
+ * plate has nothing to fit and gets the identity (support shows it); the strip that leaves the plate is replicated border
+ * and will not match the frame; the truncated weight needs the coarsest level to see the motion, so a shift well beyond
+ * a coarsest-level pixel (2^K pixels) is outside the fit's basin: it ends at the identity or, rarely, at a wrong map within
+ * `reach` (at 64 x 96, K = 2, shifts of 3.5 and 12.5 pixels do; tests/test_plate_align_host.py); the defaults are untuned on
+ * real footage.
+ * tests/plate_align_ref.py restates the definition in numpy; vm_plate_align_apply matches it bit for bit, the fit up to the
+ * order of its f64 sums.  The kernels' order is fixed (csrc/plate_align.hip: per lane in f64 registers, a wave-64 shuffle
+ * tree, the four waves in LDS, the blocks' partials in `work` added in index order; no floating-point atomics; the blocks per
+ * frame depend on the level's size only), so two runs give the same bits and a batch of n what n single calls give.
+ * vm_plate_align_fit is 1 + 2 levels iters launches for all n frames, vm_plate_align_apply one.
+ *   work     vm_plate_align_workspace_bytes(n, h, w, levels) bytes, 16-byte aligned; the call initialises what it reads
+ * bg and out may sit at any byte address; pyramids, params and support are 4-byte aligned.  No allocation, no synchronisation
+ * and no host read-back inside: the calls can be captured in a graph.  VM_EINVAL for a NULL pointer, n < 1, h or w < 16
+ * (apply: < 1) or beyond 32768, n h w 3 beyond 2^31 - 1, levels < 1, nb not 1 or n, iters outside 1..64, tol <= 0 or not
+ * finite, min_share outside 1..4096, reach outside 1..1024, a stride below one pyramid, a misaligned pyramid / params /
+ * support / work, or out overlapping bg or params (checked before any HIP call); the size query returns 0 for such shapes. */
+size_t vm_plate_align_workspace_bytes(int n, int h, int w, int levels);
+int vm_plate_align_fit(const float* cmp_pyr, long cmp_stride, const float* bg_pyr, long bg_stride, int nb, int n, int h,
+                       int w, int levels, int iters, float tol, int min_share, int reach, float* params, int32_t* support,
+                       void* work, void* stream);
+int vm_plate_align_apply(const uint8_t* bg, int nb, const float* params, int n, int h, int w, uint8_t* out, void* stream);
+
 /* ---------------------------------------------------------------- flow-compensated temporal matte filter
  * A model that mattes every frame on its own leaves mattes that shimmer along soft edges (vm_matte_score's dtSSD and
  * MESSDdt measure it).  This is a post-filter on the model's output: frame j's matte is pulled towards the previous

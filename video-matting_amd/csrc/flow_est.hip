@@ -29,6 +29,7 @@
 // pixel's update takes the centres of the rows above and below and the three rows' sums, which is hs_update's
 // additions in hs_update's order.  36 LDS reads per thread and sweep instead of 80.
 // 2 x RW x RH x 8 B = 40 KB per block, 3 blocks per CU; 132 VGPRs, no spills.
+#include "flow_pyramid.h"
 #include "vm_common.h"
 
 namespace vm {
@@ -47,31 +48,7 @@ constexpr int TX = 56, TY = 32;           // the tile a block writes (RW = 64: a
 constexpr int RW = TX + 2 * FT, RH = TY + 2 * FT, RN = RW * RH;  // the staged region
 constexpr int PPT = RN / 256;             // staged pixels per thread
 static_assert(RW == 64 && RH == 4 * PPT, "a lane is a staged column, a wave PPT staged rows");
-constexpr int MAX_LEVELS = 32, MAX_SIDE = 32768;
-
-struct Plan {
-  int n;                   // levels built
-  int h[MAX_LEVELS], w[MAX_LEVELS];
-  size_t off[MAX_LEVELS];  // floats from the pyramid's start (each a multiple of 4)
-  size_t floats;           // one pyramid
-};
-
-Plan plan_levels(int h, int w, int levels) {
-  Plan p{};
-  p.n = 1;
-  p.h[0] = h;
-  p.w[0] = w;
-  while (p.n < levels && p.n < MAX_LEVELS && (p.h[p.n - 1] < p.w[p.n - 1] ? p.h[p.n - 1] : p.w[p.n - 1]) / 2 >= 8) {
-    p.h[p.n] = (p.h[p.n - 1] + 1) / 2;
-    p.w[p.n] = (p.w[p.n - 1] + 1) / 2;
-    ++p.n;
-  }
-  for (int k = 0; k < p.n; ++k) {
-    p.off[k] = p.floats;
-    p.floats += ((size_t)p.h[k] * p.w[k] + 3) / 4 * 4;
-  }
-  return p;
-}
+constexpr int MAX_SIDE = FLOW_MAX_SIDE;
 
 size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
@@ -128,30 +105,6 @@ __global__ void __launch_bounds__(256) smooth_kernel(const float* __restrict__ a
 // the coarsest level's start (a kernel, like every step of the estimate: one chain of kernel nodes when captured)
 __global__ void __launch_bounds__(256) zero_kernel(float2* __restrict__ f, long n) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) f[i] = make_float2(0.f, 0.f);
-}
-
-// ---------------------------------------------------------------- bilinear, coordinates clamped to the image
-struct Tap {
-  long i00, i01, i10, i11;
-  float fx, fy;
-};
-
-__device__ __forceinline__ Tap tap_at(float x, float y, int h, int w) {
-  x = fminf(fmaxf(x, 0.f), (float)(w - 1));  // (a NaN coordinate becomes 0: every index stays inside)
-  y = fminf(fmaxf(y, 0.f), (float)(h - 1));
-  const float xf = floorf(x), yf = floorf(y);
-  const int x0 = (int)xf, y0 = (int)yf, x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
-  Tap t;
-  t.fx = x - xf;
-  t.fy = y - yf;
-  t.i00 = (long)y0 * w + x0; t.i01 = (long)y0 * w + x1;
-  t.i10 = (long)y1 * w + x0; t.i11 = (long)y1 * w + x1;
-  return t;
-}
-
-__device__ __forceinline__ float lerp2(float p00, float p01, float p10, float p11, float fx, float fy) {
-  const float top = p00 + fx * (p01 - p00), bot = p10 + fx * (p11 - p10);
-  return top + fy * (bot - top);
 }
 
 __global__ void __launch_bounds__(256) upsample_kernel(const float2* __restrict__ c, int ch, int cw,

@@ -223,6 +223,10 @@ SIGNATURES = [
     ("vm_plate_gain_fit", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
     ("vm_plate_gain_apply", c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("vm_plate_align_workspace_bytes", c_size_t, [c_int, c_int, c_int, c_int]),
+    ("vm_plate_align_fit", c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vm_plate_align_apply", c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("vm_matte_smooth", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
                                 c_float, c_void_p, c_void_p, c_void_p]),
 ]

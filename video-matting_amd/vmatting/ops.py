@@ -1627,6 +1627,114 @@ def plate_gain_apply(bg, gain, out=None):
     return out
 
 
+# ---------------------------------------------------------------- the plate's position matched to the frame
+
+# Gauss-Newton steps per level, the residual gate in grey levels, the share of the frame (1 / min_share) the pixels the
+# fit explains must reach, the corner displacement limit min(h, w) / reach, and the pyramids' levels: the values of a
+# CPU prototype on synthetic scenes, untuned on real footage
+ALIGN_DEFAULTS = {"iters": 4, "tol": 16.0, "min_share": 4, "reach": 6, "levels": 6}
+ALIGN_ITERS_MAX, ALIGN_SHARE_MAX, ALIGN_REACH_MAX = 64, 4096, 1024
+ALIGN_PARAMS = 7  # of the 8 floats per frame: six affine deviations and the gain
+
+
+def check_align_options(who, iters=ALIGN_DEFAULTS["iters"], tol=ALIGN_DEFAULTS["tol"],
+                        min_share=ALIGN_DEFAULTS["min_share"], reach=ALIGN_DEFAULTS["reach"],
+                        levels=ALIGN_DEFAULTS["levels"]):
+    """The options of vm_plate_align_fit as it checks them, on the host: iters in 1..64, tol a positive finite number,
+    min_share in 1..4096, reach in 1..1024, levels at least 1 -> (iters, tol, min_share, reach, levels)."""
+    iters = check_int(who, "iters", iters, 1, ALIGN_ITERS_MAX)
+    if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, (int, float, np.integer, np.floating)):
+        raise TypeError("%s: tol must be a number, got %r" % (who, tol))
+    tol = float(tol)
+    if not (tol > 0.0 and np.isfinite(tol)):
+        raise ValueError("%s: tol must be a positive finite number, got %r" % (who, tol))
+    return (iters, tol, check_int(who, "min_share", min_share, 1, ALIGN_SHARE_MAX),
+            check_int(who, "reach", reach, 1, ALIGN_REACH_MAX), check_int(who, "levels", levels, 1))
+
+
+def align_options(who, options):
+    """A dict over ALIGN_DEFAULTS (None: the defaults), checked -> {"iters": ..., "tol": ..., "min_share": ...,
+    "reach": ..., "levels": ...}."""
+    return _options(who, ALIGN_DEFAULTS, options, check_align_options)
+
+
+ALIGN_FIT = "fit"
+
+
+def check_align_mode(who, align, options):
+    """The ``align`` argument of FrameStream and reader.trimap_from_plate: None or "fit", and their ``align_options``
+    (a dict over ALIGN_DEFAULTS) only with "fit" -> the checked options, or None without an alignment."""
+    if align is not None and not (isinstance(align, str) and align == ALIGN_FIT):
+        raise ValueError("%s: align must be None or %r, got %r" % (who, ALIGN_FIT, align))
+    if align is None:
+        if options is not None:
+            raise ValueError("%s: align_options go with align=%r" % (who, ALIGN_FIT))
+        return None
+    return align_options("%s: align_options" % who, options)
+
+
+def plate_align_workspace_bytes(n, h, w, levels=ALIGN_DEFAULTS["levels"]):
+    return lib().vm_plate_align_workspace_bytes(n, h, w, levels)
+
+
+def plate_align_fit(cmp_pyr, bg_pyr, h, w, iters=ALIGN_DEFAULTS["iters"], tol=ALIGN_DEFAULTS["tol"],
+                    min_share=ALIGN_DEFAULTS["min_share"], reach=ALIGN_DEFAULTS["reach"],
+                    levels=ALIGN_DEFAULTS["levels"], out=None, support=None, work=None):
+    """vm_plate_align_fit: one affine map and one photometric gain per frame between the frames' and the plate's grey
+    pyramids.  cmp_pyr f32 [n,floats]: row i is flow_pyramid(frame i, levels) of an [h,w] frame (floats at least
+    flow_pyramid_floats(h, w, levels)); bg_pyr f32 [n,floats], or [1,floats] / [floats] for one static plate ->
+    (params f32 [n,8] = (p0..p5, g, 0), support int32 [n]): frame pixel (x, y) sees the plate at (x + p0 xc + p1 yc +
+    p2, y + p3 xc + p4 yc + p5) in centred coordinates, and is g times as bright; the identity (0 .. 0, 1, 0) where
+    fewer than h w / ``min_share`` pixels end within ``tol`` / 4 grey levels of the fit (``support`` is their count), or
+    a corner moves by more than min(h, w) / ``reach`` pixels (include/vmatting.h).  ``out`` / ``support``: contiguous
+    f32 [n,8] / int32 [n] device tensors; ``work``: a uint8 device buffer of plate_align_workspace_bytes(n, h, w,
+    levels); all allocated when None."""
+    who = "plate_align_fit"
+    h, w = check_int(who, "h", h, 1), check_int(who, "w", w, 1)
+    iters, tol, min_share, reach, levels = check_align_options(who, iters, tol, min_share, reach, levels)
+    check_flow_options(who, h, w, levels)
+    n, stride = _check_tensor(who, "cmp_pyr", cmp_pyr, (torch.float32,), "n,f")
+    shape = _check_tensor(who, "bg_pyr", bg_pyr, (torch.float32,), "n,f | 1,f | f", n=n)
+    nb = n if shape == (n, shape[-1]) else 1
+    out = _out_or_new(who, "out", out, torch.float32, "n,8", cmp_pyr.device, ValueError, n=n)
+    support = _out_or_new(who, "support", support, torch.int32, "n", cmp_pyr.device, ValueError, n=n)
+    for t in (cmp_pyr, bg_pyr, out, support):
+        _require_gpu(t)
+    floats = flow_pyramid_floats(h, w, levels)
+    if stride < floats or shape[-1] < floats:
+        raise ValueError("%s: a pyramid of [%d,%d] frames at %d levels is %d floats, got rows of %d and %d" %
+                         (who, h, w, levels, floats, stride, shape[-1]))
+    work = _buffer_or_new(who, "work", work, torch.uint8, plate_align_workspace_bytes(n, h, w, levels), cmp_pyr.device)
+    check(lib().vm_plate_align_fit(_ptr(cmp_pyr), stride, _ptr(bg_pyr), shape[-1], nb, n, h, w, levels, iters, tol,
+                                   min_share, reach, _ptr(out), _ptr(support), _ptr(work), stream_handle()), who)
+    return out, support
+
+
+def plate_align_apply(bg, params, out=None):
+    """vm_plate_align_apply: the plate seen through the maps.  bg u8 [n,h,w,3], or one static plate [h,w,3] / [1,h,w,3]
+    for all n rows of ``params`` (f32 [n,8], as plate_align_fit returns it) -> u8 [n,h,w,3]: per pixel the plate's
+    bilinear sample at the mapped position, coordinates clamped to the plate, rounded once; identity parameters return
+    the plate (include/vmatting.h).  ``out``: a contiguous uint8 [n,h,w,3] device tensor, allocated when None."""
+    who = "plate_align_apply"
+    n, _ = _check_tensor(who, "params", params, (torch.float32,), "n,8")
+    shape = _check_tensor(who, "bg", bg, (torch.uint8,), "n,h,w,3 | 1,h,w,3 | h,w,3", n=n)
+    h, w = shape[-3], shape[-2]
+    nb = n if shape == (n, h, w, 3) else 1
+    out = _out_or_new(who, "out", out, torch.uint8, "n,h,w,3", bg.device, ValueError, n=n, h=h, w=w)
+    for t in (bg, params, out):
+        _require_gpu(t)
+    check(lib().vm_plate_align_apply(_ptr(bg), nb, _ptr(params), n, h, w, _ptr(out), stream_handle()), who)
+    return out
+
+
+def frame_pyramids(frames, levels, out, work):
+    """flow_pyramid of every frame of a uint8 [n,h,w,3] stack into the rows of ``out`` (f32 [n,floats], rows 16-byte
+    aligned) -> out."""
+    for j in range(len(frames)):
+        flow_pyramid(frames[j], levels, out=out[j], work=work)
+    return out
+
+
 # ---------------------------------------------------------------- flow-compensated temporal matte filter
 
 # the share of the previous matte, the colour difference (grey levels) and the matte difference at which the gates shut:

@@ -181,6 +181,42 @@ def match_plate(cmp_u8, bg_u8, **options):
     return plate, gain.astype(np.float32) / np.float32(ops.GAIN_ONE), support.astype(np.int64)
 
 
+def _aligned_plates(cmp, bg, opts):
+    """The device side of align_plate for stacks: cmp u8 [n,h,w,3], bg u8 [n,h,w,3], [1,h,w,3] or [h,w,3] -> (the aligned plates
+    u8 [n,h,w,3], params f32 [n,8], support int32 [n])."""
+    from vmatting import ops
+    n, h, w, _ = cmp.shape
+    bg = bg[None] if bg.dim() == 3 else bg
+    levels = opts["levels"]
+    floats = (ops.flow_pyramid_floats(h, w, levels) + 3) // 4 * 4
+    work = torch.empty(ops.flow_workspace_bytes(h, w, levels), dtype=torch.uint8, device=cmp.device)
+    rows = [ops.frame_pyramids(t, levels, torch.zeros((len(t), floats), dtype=torch.float32, device=cmp.device), work)
+            for t in (cmp, bg)]
+    params, support = ops.plate_align_fit(rows[0], rows[1], h, w, **opts)
+    return ops.plate_align_apply(bg, params), params, support
+
+
+def align_plate(cmp_u8, bg_u8, **options):
+    """The background plate brought to one frame's position: what FrameStream(align="fit") puts in the plate's place.
+    cmp_u8, bg_u8 uint8 [h,w,3] BGR, h and w at least 16; ``options`` over ops.ALIGN_DEFAULTS (iters, tol, min_share,
+    reach, levels) -> (plate uint8 [h,w,3], params f32 [7] = (p0..p5, g), support int): one affine map, fitted coarse to
+    fine between the grey pyramids of frame and plate over the pixels that agree within ``tol`` grey levels, and the
+    plate resampled through it (ops.plate_align_fit, ops.plate_align_apply, include/vmatting.h).  The frame's pixel
+    (x, y) sees the plate at (x + p0 xc + p1 yc + p2, y + p3 xc + p4 yc + p5), xc = x - (w - 1) / 2, yc = y - (h - 1) /
+    2; g is the fitted photometric gain, reported and not applied.  ``support`` counts the pixels within tol / 4 of the
+    fit; below h w / min_share, or with a corner moved by more than min(h, w) / reach, the map is the identity.  One
+    global map: no parallax, no lens distortion.  numpy in, numpy out, through the kernels."""
+    from vmatting import ops
+    who = "align_plate"
+    opts = ops.align_options(who, options)
+    cmp_u8, bg_u8 = np.asarray(cmp_u8), np.asarray(bg_u8)
+    h, w, _ = ops.check_array(who, "cmp", cmp_u8, U8, "h,w,3")
+    ops.check_array(who, "bg", bg_u8, U8, "h,w,3", h=h, w=w)
+    ops.check_flow_options(who, h, w, opts["levels"])
+    plate, params, support = (_like(t, cmp_u8, True) for t in _aligned_plates(_stack(cmp_u8), _stack(bg_u8), opts))
+    return plate, params[:ops.ALIGN_PARAMS], int(support)
+
+
 def smooth_mattes(mattes, frames_u8, flows=None, **options):
     """The mattes of a clip filtered along time: what FrameStream(smooth="flow") does to the model's output, on a clip
     in host memory.  mattes f32 (clamped to [0,1]) or uint8 (q / 255) [n,h,w], the clip's frames uint8 [n,h,w,3] BGR,
@@ -215,7 +251,7 @@ def smooth_mattes(mattes, frames_u8, flows=None, **options):
 
 
 def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, fill=None, gain=None,
-                      gain_options=None):
+                      gain_options=None, align=None, align_options=None):
     """The trimap of a frame from its difference to the background plate: what FrameStream(trimap="auto") feeds the
     model, and the trimap of a clip's first frame for ClipStream's alpha0.  cmp_u8 uint8 BGR, one frame [H,W,3] or a
     stack [N,H,W,3]; bg_u8 uint8 [H,W,3] (one plate) or, with a stack, [N,H,W,3] -> uint8 [H,W] or [N,H,W]: 0 where the
@@ -223,13 +259,16 @@ def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, 
     over a (2 r_fg + 1)^2 window, 128 elsewhere (ops.trimap_from_plate, include/vmatting.h; None: ops.PLATE_DEFAULTS,
     which are untuned).  No shadow model, and no exposure model unless ``gain`` is "fit" (FrameStream's ``gain``): every
     frame is then compared with the plate under that frame's fitted gains (match_plate; ``gain_options`` over
-    ops.GAIN_DEFAULTS).  ``fill`` (FrameStream's ``auto_fill``): True, or an integer area cap, turns the enclosed
+    ops.GAIN_DEFAULTS).  No motion model unless ``align`` is "fit" (FrameStream's ``align``): the plate is first, ahead
+    of the gain, resampled through each frame's fitted affine map (align_plate; ``align_options`` over
+    ops.ALIGN_DEFAULTS; H and W at least 16).  ``fill`` (FrameStream's ``auto_fill``): True, or an integer area cap, turns the enclosed
     background of the result unknown (fill_enclosed); None or False leaves it.  numpy arrays return numpy, device tensors
     stay on the device."""
     from vmatting import ops
     who = "trimap_from_plate"
     cap = ops.check_fill(who, fill)
     gopts = ops.check_gain_mode(who, gain, gain_options)
+    aopts = ops.check_align_mode(who, align, align_options)
     if isinstance(cmp_u8, torch.Tensor) != isinstance(bg_u8, torch.Tensor):
         raise TypeError("%s: cmp and bg are both numpy arrays or both torch tensors" % who)
     given = {"lo": lo, "hi": hi, "r_bg": r_bg, "r_fg": r_fg}
@@ -243,7 +282,11 @@ def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, 
     else:
         ops.check_array(who, "bg", bg_u8, U8, "N,H,W,3 | 1,H,W,3 | H,W,3", ops.EITHER, strided=True, N=shape[0],
                         H=shape[1], W=shape[2])
+    if aopts is not None:
+        ops.check_flow_options(who, shape[-3], shape[-2], aopts["levels"])
     cmp, bg = _stack(cmp_u8, single), _stack(bg_u8, False)
+    if aopts is not None:
+        bg = _aligned_plates(cmp, bg, aopts)[0]
     if gopts is not None:
         bg = ops.plate_gain_apply(bg, ops.plate_gain_fit(cmp, bg, **gopts)[0])
     out = ops.trimap_from_plate(cmp, bg, **opts)

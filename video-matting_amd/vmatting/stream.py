@@ -25,6 +25,11 @@ frames and the plate, followed with ``auto_fill`` by ops.trimap_fill_enclosed in
 ops.plate_gain_fit and ops.plate_gain_apply: one gain per frame and colour channel, and a gained copy of the plate per
 frame, which everything after it in the chain takes for the background.
 
+``align="fit"``: the plate and the frames are not registered pixel for pixel (a bumped tripod, a handheld plate, a slow
+pan).  The chunk's chain starts, ahead of the gain, with the frames' grey pyramids, ops.plate_align_fit and
+ops.plate_align_apply: one affine map per frame, and a copy of the plate seen through it per frame, which everything
+after it in the chain takes for the background.
+
 ``scale=2..4``: the frames are larger than the model should see (2160 x 3840).  The chunk's chain reduces the uploaded
 frames (and per-frame backgrounds and trimaps) by ``scale`` (ops.frames_reduce_u8), runs the model on the reduced
 frames, and carries its matte back to the frames' size with a guided filter steered by the full-resolution frame
@@ -72,6 +77,10 @@ class _Slot(Slot):
             self.d_tri = torch.zeros((n, h, w), dtype=u8, device=fs.device)
         if fs.estimate:  # ... and so are its flows (trimap="propagate" and smooth="flow" share them)
             self.d_bw = torch.zeros((n, h, w, 2), dtype=torch.float32, device=fs.device)
+        if fs.align is not None:  # the chunk's background seen through its frames' maps, the maps and their support
+            self.a_bg = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device)
+            self.align = torch.zeros((n, 8), dtype=torch.float32, device=fs.device)
+            self.align_support = torch.zeros((n,), dtype=torch.int32, device=fs.device)
         if fs.gain is not None:  # the chunk's background under its frames' gains, the gains and their support
             self.g_bg = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device)
             self.gain = torch.zeros((n, 3), dtype=torch.int32, device=fs.device)
@@ -83,7 +92,7 @@ class _Slot(Slot):
             # filter's coefficients; the frame buffer below is then the model's size too
             h, w = fs.hm, fs.wm
             self.r_cmp = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device)
-            per_frame = fs.static_bg is None or fs.gain is not None
+            per_frame = fs.static_bg is None or fs.gain is not None or fs.align is not None
             self.r_bg = torch.zeros((n, h, w, 3), dtype=u8, device=fs.device) if per_frame else None
             self.r_tri = torch.zeros((n, h, w), dtype=u8, device=fs.device) if fs.trimap else None
             self.alpha_lo = torch.empty((n, h, w, 1), dtype=torch.float32, device=fs.device)
@@ -157,6 +166,23 @@ class FrameStream(SlotPipeline):
     it, and below h w / min_share the gain is 1; the new plate of out="over" is not gained.  gain=None is the stream
     without any of this, call for call.  ClipStream, VideoMatter and PlateEstimator do not take it.
 
+    ``align`` (None, the default, or "fit"): match the background's position to every frame before anything uses it,
+    the gain fit included.  Per frame one affine map (and, as a nuisance parameter, one photometric gain) is fitted
+    between the grey pyramids of the frame and of the background (the static plate, or the item's per-frame ``bg``) on
+    the device, coarse to fine over the pixels that agree within ``tol`` grey levels (ops.plate_align_fit,
+    ``align_options`` a dict over ops.ALIGN_DEFAULTS: iters, tol, min_share, reach, levels; untuned on real footage; h
+    and w at least 16), and a copy of the background resampled through the map (ops.plate_align_apply) stands in for it
+    in the rest of the chain: the gain fit, the automatic trimap, the model's feed (with ``scale`` its reduction) and
+    the compose modes.  The mattes are those of a stream fed these aligned backgrounds as per-frame ``bg``, bit for
+    bit; reader.align_plate shows one.  Where the stream estimates flows (smooth="flow", trimap="propagate") at the
+    same ``levels``, the frames' pyramids are the flow estimate's own and are not built twice.  ``last_alignment()``
+    returns the last chunk's maps and their support after a run.  What it is not: one global affine map per frame, so
+    no parallax, no rolling shutter, no lens distortion; a textureless plate has nothing to fit and keeps its place
+    (``support`` is 0); so does a frame in which fewer than h w / min_share pixels end within tol / 4 of the fit, and
+    one whose fitted corners move by more than min(h, w) / reach; the strip that leaves the plate is replicated border
+    and will not be labelled background; the new plate of out="over" is not moved.  align=None is the stream without
+    any of this, call for call.  ClipStream, VideoMatter and PlateEstimator do not take it.
+
     ``smooth`` (None, the default, or "flow"): filter the mattes along time before they are quantised or composed.
     After the forward (and, with ``scale``, the upsampling) frame j's matte is pulled towards the filtered matte of
     frame j - 1, sampled where frame j's backward flow says each pixel came from, by ``strength`` times a weight that
@@ -183,7 +209,7 @@ class FrameStream(SlotPipeline):
 
     def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True, new_bg=None,
                  flow=None, flow_options=None, grow=1, auto_options=None, auto_fill=None, scale=1, guided_options=None,
-                 gain=None, gain_options=None, smooth=None, smooth_options=None):
+                 gain=None, gain_options=None, smooth=None, smooth_options=None, align=None, align_options=None):
         h, w, chunk, depth = int(h), int(w), int(chunk), int(depth)
         if h < 1 or w < 1 or chunk < 1 or depth < 1:
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
@@ -233,6 +259,10 @@ class FrameStream(SlotPipeline):
             self.flow_options = flow_options
         # gain="fit": the fit's options (None: no gain)
         self.gain = ops.check_gain_mode("FrameStream", gain, gain_options)
+        # align="fit": the fit's options (None: no alignment)
+        self.align = ops.check_align_mode("FrameStream", align, align_options)
+        if self.align is not None:
+            ops.check_flow_options("FrameStream: align", h, w, self.align["levels"])
         # the plates
         static_bg = check_static_bg("FrameStream", static_bg, h, w)
         self.new_bg = check_new_bg("FrameStream", out, new_bg, h, w)
@@ -242,6 +272,9 @@ class FrameStream(SlotPipeline):
         self.overflowed_chunks = []
         self._plate_lo = self._guided_work = None  # scale > 1: the reduced plate, the guided filter's workspace
         self._gain_work = self._gain_last = None   # gain="fit": the fit's workspace; the last chunk's (slot, frames)
+        # align="fit": the fit's workspace, the pyramids of the chunk's frames (None: the flow tracker's) and of its
+        # backgrounds (one row for a static plate), the pyramids' workspace, and the last chunk's (slot, frames)
+        self._align_work = self._align_rows = self._align_bg_rows = self._align_pyr_work = self._align_last = None
         self._x6 = None
         self._keyed = False      # trimap="propagate": whether this run has had its first key
         self._tri_last = None    # ... and the last frame's trimap, at a fixed device address
@@ -307,7 +340,8 @@ class FrameStream(SlotPipeline):
         self._make_streams()
         self._upload_plates()
         if self.scale > 1:  # the plate at the model's size, once; one workspace for every slot, like _auto_work
-            if self._plate is not None and self.gain is None:  # (a gained plate is reduced per chunk)
+            if self._plate is not None and self.gain is None and self.align is None:  # (a gained or aligned plate is
+                #                                                                       reduced per chunk)
                 self._plate_lo = ops.frames_reduce_u8(self._plate[None], self.scale)
             self._guided_work = torch.zeros(ops.guided_workspace_bytes(self.chunk, self.hm, self.wm), dtype=torch.uint8,
                                             device=self.device)
@@ -316,6 +350,8 @@ class FrameStream(SlotPipeline):
                                           device=self.device)
         if self.estimate:  # the pyramids of the previous chunk's last frame and of this chunk's, once for every slot
             self._flow = FlowTracker(self.h, self.w, self.flow_options, self.device, frames=self.chunk)
+        if self.align is not None:
+            self._setup_align()
         if self.propagate:
             self._setup_propagate()
         if self.smooth is not None:
@@ -346,6 +382,21 @@ class FrameStream(SlotPipeline):
         self._tri_last = torch.zeros((h, w), dtype=torch.uint8, device=dev)
         self._tri_work = torch.zeros(max(ops.trimap_propagate_workspace_bytes(h, w, self.grow), 1), dtype=torch.uint8,
                                      device=dev)
+
+    def _setup_align(self):
+        """What the alignment needs besides the slots' buffers, once for every slot: the fit's workspace, the rows of
+        the frames' pyramids unless the flow tracker makes them anyway (the same levels), the rows of the backgrounds'
+        pyramids - one, filled here, for a static plate - and the pyramids' workspace."""
+        dev, h, w, n, levels = self.device, self.h, self.w, self.chunk, self.align["levels"]
+        floats = (ops.flow_pyramid_floats(h, w, levels) + 3) // 4 * 4  # every row 16-byte aligned
+        rows = lambda k: torch.zeros((k, floats), dtype=torch.float32, device=dev)  # noqa: E731
+        self._align_work = torch.zeros(ops.plate_align_workspace_bytes(n, h, w, levels), dtype=torch.uint8, device=dev)
+        self._align_pyr_work = torch.zeros(ops.flow_workspace_bytes(h, w, levels), dtype=torch.uint8, device=dev)
+        if not (self.estimate and self.flow_options["levels"] == levels):
+            self._align_rows = rows(n)
+        self._align_bg_rows = rows(1 if self._plate is not None else n)
+        if self._plate is not None:
+            ops.frame_pyramids(self._plate[None], levels, self._align_bg_rows, self._align_pyr_work)
 
     def _setup_smooth(self):
         """What the temporal filter keeps between chunks, once for every slot and at fixed addresses like the trimap
@@ -417,10 +468,45 @@ class FrameStream(SlotPipeline):
         return (s.gain[:k].cpu().numpy().astype(np.float32) / np.float32(ops.GAIN_ONE),
                 s.support[:k].cpu().numpy().astype(np.int64))
 
+    def last_alignment(self):
+        """align="fit": (params f32 [k,7] = (p0..p5, g), support int [k]) of the last chunk submitted, once the run
+        has drained: frame pixel (x, y) sees the plate at (x + p0 xc + p1 yc + p2, y + p3 xc + p4 yc + p5), xc = x -
+        (w - 1) / 2, yc = y - (h - 1) / 2; (0 .. 0, 1) is the identity."""
+        if self.align is None:
+            raise ValueError("FrameStream: last_alignment() goes with align='fit'")
+        if self._align_last is None:
+            raise RuntimeError("FrameStream: last_alignment() before any frame was submitted")
+        s, k = self._align_last
+        return (s.align[:k, :ops.ALIGN_PARAMS].cpu().numpy(), s.align_support[:k].cpu().numpy().astype(np.int64))
+
+    def _aligned(self, s, k):
+        """The background before the gain: the plate, the uploaded per-frame backgrounds, or with align="fit" the slot's
+        aligned copy (made by _align)."""
+        return s.a_bg[:k] if self.align is not None else self._plates(s, k)[0]
+
     def _background(self, s, k):
-        """What the chain of the slot's first k frames takes for the background: the plate, the uploaded per-frame
-        backgrounds, or with gain="fit" the slot's gained copy (made by _before)."""
-        return s.g_bg[:k] if self.gain is not None else self._plates(s, k)[0]
+        """What the chain of the slot's first k frames takes for the background: _aligned, or with gain="fit" the
+        slot's gained copy of it (made by _before)."""
+        return s.g_bg[:k] if self.gain is not None else self._aligned(s, k)
+
+    def _align(self, s, k):
+        """align="fit": the maps of the slot's first k frames and the background seen through them into s.a_bg, on the
+        current stream: the frames' pyramids (the flow tracker's where _flows has just made them), with per-frame
+        backgrounds theirs, the fit, the resampling."""
+        if self.align is None:
+            return
+        o, bg = self.align, self._plates(s, k)[0]
+        if self._align_rows is None:
+            cmp_rows = self._flow.rows[1:k + 1]
+        else:
+            cmp_rows = ops.frame_pyramids(s.d_cmp[:k], o["levels"], self._align_rows[:k], self._align_pyr_work)
+        if self._plate is None:
+            bg_rows = ops.frame_pyramids(bg, o["levels"], self._align_bg_rows[:k], self._align_pyr_work)
+        else:
+            bg_rows = self._align_bg_rows
+        ops.plate_align_fit(cmp_rows, bg_rows, self.h, self.w, out=s.align[:k], support=s.align_support[:k],
+                            work=self._align_work, **o)
+        ops.plate_align_apply(bg, s.align[:k], out=s.a_bg[:k])
 
     def _feed(self, s, k, bg):
         """The network input of the slot's first k frames from its uint8 frames; with scale > 1 from their reductions."""
@@ -454,14 +540,16 @@ class FrameStream(SlotPipeline):
 
     def _before(self, s, k, keyed):
         """What the chain of the slot's first k frames runs before the forward, on the current stream: with
-        gain="fit" the gains and the gained background, with flow="estimate" the frames' flows, with
-        trimap="propagate" or "auto" their trimaps, then the ingest.  ``keyed``: the item restarts the chain's state."""
+        flow="estimate" the frames' flows, with align="fit" the maps and the aligned background, with gain="fit" the
+        gains and the gained background, with trimap="propagate" or "auto" their trimaps, then the ingest.  ``keyed``:
+        the item restarts the chain's state."""
+        self._flows(s, k, keyed)  # (first: the alignment reads the frames' pyramids it leaves behind)
+        self._align(s, k)
         if self.gain is not None:
-            bg = self._plates(s, k)[0]
+            bg = self._aligned(s, k)
             ops.plate_gain_fit(s.d_cmp[:k], bg, out=s.gain[:k], support=s.support[:k], work=self._gain_work, **self.gain)
             ops.plate_gain_apply(bg, s.gain[:k], out=s.g_bg[:k])
         bg = self._background(s, k)
-        self._flows(s, k, keyed)
         if self.propagate:
             self._trimaps(s, k, keyed)
         if self.auto:
@@ -500,6 +588,8 @@ class FrameStream(SlotPipeline):
         s.k, s.index = k, index
         if self.gain is not None:
             self._gain_last = (s, k)
+        if self.align is not None:
+            self._align_last = (s, k)
         # the item restarts the chain's state: it carries a key, or without trimap="propagate" it is a run's first
         keyed = tri is not None if self.propagate else self.smooth is not None and not self._started
         self._started, self._smooth_k = True, k
