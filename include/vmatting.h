@@ -748,7 +748,8 @@ int vm_trimap_propagate(const uint8_t* prev, const float* flow, int h, int w, in
  *   out   uint8 [n,h,w]: 255 where F, 0 where B, 128 elsewhere (lo < hi: the two exclude each other); it must not
  *         overlap cmp or bg
  * What this is not: it has no shadow or exposure model (a shadow on the plate or a gain change is a difference like
- * any other; vm_plate_gain_fit / vm_plate_gain_apply below match the plate's exposure to the frame before this call).  It cannot tell a translucent high-contrast pixel from an opaque one, so r_fg must exceed the width of
+ * any other; vm_trimap_from_plate_shadow below tolerates cast shadows, and vm_plate_gain_fit / vm_plate_gain_apply
+ * further down match the plate's exposure to the frame before this call).  It cannot tell a translucent high-contrast pixel from an opaque one, so r_fg must exceed the width of
  * the soft edge.  Foreground that matches the plate over an area wider than 2 r_bg + 1 is labelled background.
  * tests/trimap_plate_ref.py restates the definition in numpy; the kernels match it byte for byte.
  * Two launches for all n frames (csrc/trimap_plate.hip): the candidates B0 and F0 as bit rows into `work` (0.25 B per
@@ -761,6 +762,42 @@ int vm_trimap_propagate(const uint8_t* prev, const float* flow, int h, int w, in
 size_t vm_trimap_from_plate_workspace_bytes(int n, int h, int w);
 int vm_trimap_from_plate(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int h, int w, int lo, int hi, int r_bg,
                          int r_fg, uint8_t* out, void* work, void* stream);
+
+/* The same trimap with a distance that tolerates cast shadows: the brightness / chromaticity split of Horprasert et
+ * al. (1999).  A shadowed background pixel is the plate's colour scaled by a factor below 1, so where the frame's
+ * pixel lies close to the line through the plate's colour, and the factor is one a shadow may have, the distance to
+ * that line replaces the distance to the plate itself.  trimap_from_plate_shadow(cmp, bg, lo, hi, r_bg, r_fg, floor,
+ * ceil, dark) = out is trimap_from_plate with d' in place of d; per pixel, with I = cmp's three bytes and E = bg's, all
+ * integer:
+ *   d         sum over c of (I_c - E_c)^2, as above
+ *   ee, ie, ii   sum over c of E_c^2, of I_c E_c, of I_c^2
+ *   cross     ii ee - ie^2: >= 0 (Cauchy-Schwarz), up to about 3.8e10, so 64 bits
+ *   in range  ee >= max(3 dark^2, 1)  and  floor ee <= 256 ie <= ceil ee
+ *   d'        cross / ee rounded down where in range, d elsewhere.  cross / ee is the squared distance of I from the
+ *             line through E, so d' <= d everywhere
+ *   floor     1..256: the least share of the light, in 1/256, that a shadow may leave (128)
+ *   ceil      256..512, floor <= ceil: the most; above 256 a highlight passes too (256)
+ *   dark      0..255: the plate's mean level below which its chromaticity is not trusted (32)
+ * The box sum D of d', the thresholds, the erosions and the labels are those of vm_trimap_from_plate, and so are the
+ * buffers, the workspace size and the two launches (SHADOW instantiation of the candidates kernel: the quotient is an
+ * f32 reciprocal estimate settled by an integer remainder, exact).  tests/plate_shadow_ref.py restates it in numpy; the
+ * kernels match it byte for byte.  The values in brackets are the wrappers' defaults: those of a numpy prototype,
+ * untuned on real footage.  On its synthetic scene (tests/plate_shadow_ref.py, 20 seeds) a soft shadow that keeps 0.8
+ * or 0.6 of the light has none of its core labelled 0 by vm_trimap_from_plate, and at 0.6 up to 476 background pixels
+ * per frame labelled 255; with d' 0.72-0.84 of the core is labelled 0, no pixel with alpha > 0 is labelled 0 and none
+ * with alpha < 1 is labelled 255.
+ * What this is not: a per-pixel colour test, so a subject that is a darker version of the plate's own hue passes as
+ * shadow and is labelled background (a dark-grey shirt on a light-grey wall, any grey on any grey: a 110-grey square
+ * on a flat 180-grey plate is labelled 0 throughout; vm_trimap_fill_enclosed repairs only an enclosed one).  There is
+ * no smoothness or texture test of the light ratio and no temporal test.  A shadow deeper than floor, or within noise
+ * of it, falls back to d, and one such pixel costs its whole (2 r_bg + 3)^2 neighbourhood (with floor 128 a 0.6
+ * shadow holds; a 0.45 shadow with floor 100 mostly does not).  Plate pixels darker than dark get no tolerance.  Only
+ * the trimap changes: the model still sees the shadowed frame against the unshadowed plate, and a composite onto a new
+ * plate carries the shadow additively (cmp - bg), not as a multiplicative shadow pass.
+ * VM_EINVAL as vm_trimap_from_plate, and for floor, ceil or dark out of range (floor <= 256 <= ceil by their ranges). */
+int vm_trimap_from_plate_shadow(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int h, int w, int lo, int hi,
+                                int r_bg, int r_fg, int floor, int ceil, int dark, uint8_t* out, void* work,
+                                void* stream);
 
 /* ---------------------------------------------------------------- connected components, and enclosed background
  * components_label(mask, value, connectivity) = labels, per frame:

@@ -10,10 +10,12 @@ trimap="propagate" on given flows and on estimated ones, interleaved in one proc
 writes profiles/trimap_propagate.json.  The auto section (``--sections auto``) measures vm_trimap_from_plate for one
 frame and for a chunk at radii (0, 0), the defaults and (32, 32) against its bytes model and against the same
 definition in torch ops (equal bytes asserted), and FrameStream(trimap="auto") beside per-frame trimaps, interleaved; it
-prints a JSON line and writes profiles/trimap_auto.json.
+prints a JSON line and writes profiles/trimap_auto.json.  Its last leg (alone with ``--sections shadow``) measures the
+same call with the shadow-tolerant distance beside the plain one, in turn in one run, and FrameStream(trimap="auto") with
+and without shadow="chroma", interleaved; it prints a JSON line and writes profiles/plate_shadow.json.
 
     python tools/stream_bench.py [--frames 64] [--chunk 8] [--height 1080] [--width 1920] [--reps 9]
-                                 [--sections ingest,compose,propagate,auto] [--propagate-sizes 500x1200,1080x1920]
+                                 [--sections ingest,compose,propagate,auto,shadow] [--propagate-sizes 500x1200,1080x1920]
 
 Kernel times are hipEvent medians over ``--reps`` runs after a warm-up; every run of a kernel works on another of
 several buffer sets, so the 83 MB alpha of the quantise kernel does not sit in the 256 MB memory-side cache between
@@ -503,6 +505,106 @@ def auto_section(a):
     with open(a.auto_out, "w") as f:
         f.write(line + "\n")
     print(line)
+    del model
+    torch.cuda.empty_cache()
+    shadow_leg(a)
+
+
+def spread(times, per=1):
+    """Median, min and max of a list of times, each divided by ``per``."""
+    return {"median": round(statistics.median(times) / per, 4), "min": round(min(times) / per, 4),
+            "max": round(max(times) / per, 4), "runs": len(times)}
+
+
+def shadow_leg(a):
+    """The shadow-tolerant distance beside the plain one (``--sections shadow`` runs this leg alone):
+    ops.trimap_from_plate at [1 | chunk, height, width] with the defaults, plain and with shadow=SHADOW_DEFAULTS in turn,
+    round by round in one run, and FrameStream(trimap="auto") with and without shadow="chroma", interleaved."""
+    from vmatting import FrameStream, ops, unet
+    from vmatting.weights import synthetic_vgg16
+    h, w, F = a.height, a.width, a.frames
+    hw = h * w
+    res = {"height": h, "width": w, "chunk": a.chunk, "frames": F, "reps": a.reps,
+           "device": torch.cuda.get_device_name(0), "bytes_per_pixel": AUTO_BYTES_PER_PIXEL,
+           "defaults": dict(ops.PLATE_DEFAULTS), "shadow_defaults": dict(ops.SHADOW_DEFAULTS)}
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0)
+    modes = {"plain": None, "shadow": dict(ops.SHADOW_DEFAULTS)}
+
+    def frames(n, nsets):
+        """auto_section's frames with the lower left third of every frame at 0.7 of its light: a shadow that the plain
+        distance calls a difference and the shadow distance does not."""
+        bg = torch.randint(32, 256, (nsets, n, (h + 63) // 64, (w + 63) // 64, 3), generator=g, device="cuda",
+                           dtype=torch.uint8).repeat_interleave(64, 2).repeat_interleave(64, 3)[:, :, :h, :w].contiguous()
+        cmp = bg ^ torch.randint(0, 4, bg.shape, generator=g, device="cuda", dtype=torch.uint8)
+        cmp[:, :, h // 4:3 * h // 4, w // 3:2 * w // 3] ^= 0x80
+        cmp[:, :, h // 2:, :w // 3] = (cmp[:, :, h // 2:, :w // 3].float() * 0.7).round().to(torch.uint8)
+        return cmp, bg
+
+    def kernels():
+        out = {}
+        for n in (1, a.chunk):
+            nsets = max(a.sets, int(300e6 / (AUTO_BYTES_PER_PIXEL * n * hw)) + 1)
+            cmp, bg = frames(n, nsets)
+            outs = torch.empty((nsets, n, h, w), dtype=torch.uint8, device="cuda")
+            work = torch.empty(ops.trimap_from_plate_workspace_bytes(n, h, w), dtype=torch.uint8, device="cuda")
+            times = {mode: [] for mode in modes}
+            for _ in range(5):  # the two calls in turn, five rounds
+                for mode, shadow in modes.items():
+                    times[mode].append(graph_ms([lambda i=i: ops.trimap_from_plate(cmp[i], bg[i], out=outs[i], work=work,
+                                                                                   shadow=shadow)
+                                                 for i in range(nsets)], a.reps, calls=200))
+            per = {"buffer_sets": nsets}
+            for mode, shadow in modes.items():
+                tri = ops.trimap_from_plate(cmp[0], bg[0], shadow=shadow)
+                per[mode] = dict(rate(n * hw * AUTO_BYTES_PER_PIXEL, statistics.median(times[mode])), ms_spread=spread(times[mode]),
+                                 label_shares=[round(float((tri == v).float().mean()), 3) for v in (0, 128, 255)])
+            per["shadow_over_plain"] = round(per["shadow"]["ms"] / per["plain"]["ms"], 3)
+            out["n%d" % n] = per
+            del cmp, bg, outs, work
+            torch.cuda.empty_cache()
+        return out
+    res["kernels"] = step("shadow kernels", a.step_limit, kernels)
+    torch.cuda.empty_cache()
+
+    np.random.seed(0)
+    model = unet.UNetVideo(synthetic_vgg16(0), dtype="bf16", device="cuda").prepare()
+
+    def streamed():
+        n = a.chunk
+        k = min(F, 2 * n)
+        cmp, bg = (t[0].cpu().numpy() for t in frames(k, 1))
+        torch.cuda.empty_cache()
+
+        def source():
+            for i in range(0, F, n):
+                m, s = min(n, F - i), i % k
+                yield cmp[s:s + m], bg[s:s + m], None
+        kw = dict(chunk=n, depth=2, out="u8", trimap="auto")
+        streams = {"auto": FrameStream(model, h, w, **kw), "auto_shadow": FrameStream(model, h, w, shadow="chroma", **kw)}
+
+        def run(mode):
+            t0 = time.perf_counter()
+            tot = sum(m.shape[0] for m in streams[mode].run(source()))
+            torch.cuda.synchronize()
+            assert tot == F
+            return (time.perf_counter() - t0) * 1e3
+        times = {mode: [] for mode in streams}
+        for i in range(1 + max(3, a.reps // 2)):  # interleaved; round 0 warms up (and captures the graphs)
+            for mode in streams:
+                ms = run(mode)
+                if i:
+                    times[mode].append(ms)
+        out = {"frame_stream_bf16_trimap_" + mode: {"ms_per_frame": spread(t, F)} for mode, t in times.items()}
+        out["shadow_adds_ms_per_frame"] = round(out["frame_stream_bf16_trimap_auto_shadow"]["ms_per_frame"]["median"] -
+                                                out["frame_stream_bf16_trimap_auto"]["ms_per_frame"]["median"], 4)
+        return out
+    res["streams"] = step("shadow streams", a.step_limit, streamed)
+    line = json.dumps(res)
+    os.makedirs(os.path.dirname(a.shadow_out), exist_ok=True)
+    with open(a.shadow_out, "w") as f:
+        f.write(line + "\n")
+    print(line)
 
 
 def main():
@@ -519,11 +621,14 @@ def main():
     ap.add_argument("--propagate-out", default=os.path.join(REPO, "profiles", "trimap_propagate.json"))
     ap.add_argument("--propagate-sizes", default="500x1200,1080x1920", help="comma-separated HxW of the propagate section")
     ap.add_argument("--auto-out", default=os.path.join(REPO, "profiles", "trimap_auto.json"))
-    ap.add_argument("--sections", default="ingest,compose", help="comma-separated: ingest, compose, propagate, auto")
+    ap.add_argument("--shadow-out", default=os.path.join(REPO, "profiles", "plate_shadow.json"))
+    ap.add_argument("--sections", default="ingest,compose",
+                    help="comma-separated: ingest, compose, propagate, auto, shadow (the auto section's last leg alone)")
     a = ap.parse_args()
     sections = set(a.sections.split(","))
-    if not sections or sections - {"ingest", "compose", "propagate", "auto"}:
-        raise SystemExit("stream_bench: --sections takes ingest, compose, propagate and / or auto, got %r" % a.sections)
+    if not sections or sections - {"ingest", "compose", "propagate", "auto", "shadow"}:
+        raise SystemExit("stream_bench: --sections takes ingest, compose, propagate, auto and / or shadow, got %r" %
+                         a.sections)
     if not torch.cuda.is_available():
         raise SystemExit("stream_bench needs a ROCm GPU")
     if "ingest" in sections:
@@ -537,6 +642,8 @@ def main():
         torch.cuda.empty_cache()
     if "auto" in sections:
         auto_section(a)
+    elif "shadow" in sections:
+        shadow_leg(a)
 
 
 def ingest_section(a):

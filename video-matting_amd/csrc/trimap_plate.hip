@@ -10,7 +10,9 @@
 //       down to 4; bytewise for a plane that is not 4-byte aligned and for the plane's last, partial dword), PLANE_BATCH
 //       rows of both planes in flight per thread, and unpacked from LDS into a tile of d with a 1-pixel halo, whose
 //       border entries are the clamped pixels: every box sum is then 9 plain terms.  One thread per column walks its 16
-//       rows with the three row sums in registers; a wave is one word, its two ballots one 16-byte store.
+//       rows with the three row sums in registers; a wave is one word, its two ballots one 16-byte store.  For
+//       vm_trimap_from_plate_shadow the tile holds the shadow-tolerant d' (shadow_distance below) in place of d: the
+//       SHADOW instantiation, which differs in that one value only.
 //   erode and emit  a block takes 128 x 32 pixels with a halo of max(r_bg, r_fg) rows and one word each side (r <= 32 <
 //       64) in LDS.  Row erosion is shifts and ANDs across the left, middle and right word, column erosion an AND down
 //       2 r + 1 rows, each class with its own radius; words and rows outside the image are all ones.  Every thread then
@@ -27,6 +29,7 @@ namespace vm {
 namespace {
 
 constexpr int R_MAX = 32, LEVEL_MAX = 442;        // 442^2 >= 3 * 255^2: no distance reaches beyond it
+constexpr int SHADOW_ONE = 256;                   // floor and ceil are light ratios in 1/256
 constexpr int CAND_WORDS = 4, CAND_COLS = CAND_WORDS * 64, CAND_ROWS = 16;
 constexpr int CAND_HALO = CAND_ROWS + 2, PLANE_BATCH = 6;
 static_assert(CAND_HALO % PLANE_BATCH == 0, "the halo rows are staged in whole batches");
@@ -58,12 +61,44 @@ __device__ __forceinline__ uint32_t plane_tail(const uint8_t* __restrict__ p, si
   return v;
 }
 
-// work: [n][h][words][2] 64-bit, words = ceil(w / 64): {background, foreground} candidate bits
-template <bool VEC>
+// the shadow-tolerant distance d' of one pixel (the definition: include/vmatting.h): floor(cross / ee), the squared
+// distance of I from the line through E, where the plate is bright enough (ee >= ee_min >= 1) and the light ratio ie /
+// ee lies within [lo256, hi256] / 256; the plain d elsewhere.  Branch-free: every lane computes both and selects.  The
+// floor quotient q <= ii < 2^18 comes from an f32 estimate: (float)cross, v_rcp_f32 (1 ulp) and the product are each
+// within 2^-23 relative, so the estimate is within 2^18 * 2^-21.4 < 0.1 of cross / ee and its truncation within 1 of q.
+// The remainder cross - q0 ee then lies in (-ee, 2 ee), inside int32, so its low 32 bits are exact and one step either
+// way settles q.
+__device__ __forceinline__ int shadow_distance(const uint8_t* __restrict__ pc, const uint8_t* __restrict__ pb, int d,
+                                               int lo256, int hi256, int ee_min) {
+  uint32_t ee = 0, ie = 0, ii = 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const uint32_t i = pc[c], e = pb[c];
+    ee += e * e;
+    ie += i * e;
+    ii += i * i;
+  }
+  // floor ee <= 256 ie <= ceil ee: all below 2^27
+  const bool in_range = ee >= (uint32_t)ee_min && (uint32_t)lo256 * ee <= 256u * ie && 256u * ie <= (uint32_t)hi256 * ee;
+  const unsigned long long cross = (unsigned long long)ii * ee - (unsigned long long)ie * ie;  // >= 0 (Cauchy-Schwarz)
+  const uint32_t den = ee ? ee : 1u;                                                          // (not in range then)
+  uint32_t q = (uint32_t)((float)cross * __builtin_amdgcn_rcpf((float)den));
+  int r = (int)((uint32_t)cross - q * den);
+  if (r < 0) {
+    --q;
+    r += (int)den;
+  }
+  if (r >= (int)den) ++q;
+  return in_range ? (int)q : d;
+}
+
+// work: [n][h][words][2] 64-bit, words = ceil(w / 64): {background, foreground} candidate bits.  SHADOW: the tile holds
+// d' (shadow_distance) in place of d; nothing else differs.
+template <bool VEC, bool SHADOW>
 __global__ void __launch_bounds__(256)
 plate_candidates_kernel(const uint8_t* __restrict__ cmp, const uint8_t* __restrict__ bg, int nb, int h, int w, int words,
                         int tiles_x, int tiles_y, int d_lo, int d_hi, size_t cmp_bytes, size_t bg_bytes,
-                        unsigned long long* __restrict__ work) {
+                        unsigned long long* __restrict__ work, int lo256, int hi256, int ee_min) {
   __shared__ uint32_t raw[PLANE_BATCH][2][SEG_DWORDS];
   __shared__ int dist[CAND_HALO][CAND_COLS + 2];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -120,7 +155,7 @@ plate_candidates_kernel(const uint8_t* __restrict__ cmp, const uint8_t* __restri
         const int q = (int)pc[c] - (int)pb[c];
         s += q * q;
       }
-      dist[j0 + u][e] = s;
+      dist[j0 + u][e] = SHADOW ? shadow_distance(pc, pb, s, lo256, hi256, ee_min) : s;
     }
     __syncthreads();
   }
@@ -232,9 +267,12 @@ extern "C" size_t vm_trimap_from_plate_workspace_bytes(int n, int h, int w) {
   return (size_t)n * h * row_words(w) * 16;
 }
 
-extern "C" int vm_trimap_from_plate(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int h, int w, int lo, int hi,
-                                    int r_bg, int r_fg, uint8_t* out, void* work, void* stream) {
-  const char* who = "trimap_from_plate";
+namespace {
+
+// both entry points: shadow == false is the plain distance (floor, ceil and dark are not looked at)
+int trimap_from_plate(const char* who, const uint8_t* cmp, const uint8_t* bg, int nb, int n, int h, int w, int lo, int hi,
+                      int r_bg, int r_fg, bool shadow, int floor, int ceil, int dark, uint8_t* out, void* work,
+                      void* stream) {
   if (n < 1 || h < 1 || w < 1) return fail(VM_EINVAL, "%s: bad shape [%d,%d,%d]", who, n, h, w);
   if (!shape_ok(n, h, w)) return fail(VM_EINVAL, "%s: %d x %d x %d pixels exceed %d", who, n, h, w, INT_MAX);
   if (nb != 1 && nb != n) return fail(VM_EINVAL, "%s: %d background frames for %d frames (1 or n)", who, nb, n);
@@ -242,6 +280,12 @@ extern "C" int vm_trimap_from_plate(const uint8_t* cmp, const uint8_t* bg, int n
     return fail(VM_EINVAL, "%s: lo %d, hi %d (0 <= lo < hi <= %d)", who, lo, hi, LEVEL_MAX);
   if (r_bg < 0 || r_bg > R_MAX || r_fg < 0 || r_fg > R_MAX)
     return fail(VM_EINVAL, "%s: r_bg %d, r_fg %d (0..%d)", who, r_bg, r_fg, R_MAX);
+  if (shadow) {
+    if (floor < 1 || floor > SHADOW_ONE || ceil < SHADOW_ONE || ceil > 2 * SHADOW_ONE)
+      return fail(VM_EINVAL, "%s: floor %d, ceil %d (1 <= floor <= %d <= ceil <= %d)", who, floor, ceil, SHADOW_ONE,
+                  2 * SHADOW_ONE);
+    if (dark < 0 || dark > 255) return fail(VM_EINVAL, "%s: dark %d (0..255)", who, dark);
+  }
   if (!cmp || !bg || !out || !work) return fail(VM_EINVAL, "%s: null cmp / bg / out / work", who);
   const size_t pixels = (size_t)n * h * w, cmp_bytes = pixels * 3, bg_bytes = (size_t)nb * h * w * 3;
   if (overlap(out, pixels, cmp, cmp_bytes) || overlap(out, pixels, bg, bg_bytes))
@@ -254,15 +298,29 @@ extern "C" int vm_trimap_from_plate(const uint8_t* cmp, const uint8_t* bg, int n
     const int tiles_x = (words + CAND_WORDS - 1) / CAND_WORDS, tiles_y = (h + CAND_ROWS - 1) / CAND_ROWS;
     const dim3 grid((unsigned)tiles_x * tiles_y * n);  // (at most n h w tiles: within int)
     const bool vec = reinterpret_cast<uintptr_t>(cmp) % 4 == 0 && reinterpret_cast<uintptr_t>(bg) % 4 == 0 && bg_bytes >= 4;
-    if (vec)
-      hipLaunchKernelGGL((plate_candidates_kernel<true>), grid, dim3(256), 0, st, cmp, bg, nb, h, w, words, tiles_x,
-                         tiles_y, 9 * lo * lo, 9 * hi * hi, cmp_bytes, bg_bytes, rows);
-    else
-      hipLaunchKernelGGL((plate_candidates_kernel<false>), grid, dim3(256), 0, st, cmp, bg, nb, h, w, words, tiles_x,
-                         tiles_y, 9 * lo * lo, 9 * hi * hi, cmp_bytes, bg_bytes, rows);
+    const int ee_min = shadow && dark > 0 ? 3 * dark * dark : 1;
+    auto kernel = shadow ? (vec ? plate_candidates_kernel<true, true> : plate_candidates_kernel<false, true>)
+                         : (vec ? plate_candidates_kernel<true, false> : plate_candidates_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, cmp, bg, nb, h, w, words, tiles_x, tiles_y, 9 * lo * lo,
+                       9 * hi * hi, cmp_bytes, bg_bytes, rows, floor, ceil, ee_min);
   }
   const int tiles_x = (words + ERODE_WORDS - 1) / ERODE_WORDS, tiles_y = (h + ERODE_ROWS - 1) / ERODE_ROWS;
   hipLaunchKernelGGL(plate_erode_emit_kernel, dim3((unsigned)tiles_x * tiles_y * n), dim3(256), 0, st, rows, h, w, words,
                      tiles_x, tiles_y, r_bg, r_fg, out);
   return check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int vm_trimap_from_plate(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int h, int w, int lo, int hi,
+                                    int r_bg, int r_fg, uint8_t* out, void* work, void* stream) {
+  return trimap_from_plate("trimap_from_plate", cmp, bg, nb, n, h, w, lo, hi, r_bg, r_fg, false, 0, 0, 0, out, work,
+                           stream);
+}
+
+extern "C" int vm_trimap_from_plate_shadow(const uint8_t* cmp, const uint8_t* bg, int nb, int n, int h, int w, int lo,
+                                           int hi, int r_bg, int r_fg, int floor, int ceil, int dark, uint8_t* out,
+                                           void* work, void* stream) {
+  return trimap_from_plate("trimap_from_plate_shadow", cmp, bg, nb, n, h, w, lo, hi, r_bg, r_fg, true, floor, ceil, dark,
+                           out, work, stream);
 }

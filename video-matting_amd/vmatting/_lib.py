@@ -207,6 +207,8 @@ SIGNATURES = [
     ("vm_trimap_from_plate_workspace_bytes", c_size_t, [c_int, c_int, c_int]),
     ("vm_trimap_from_plate", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                      c_void_p, c_void_p]),
+    ("vm_trimap_from_plate_shadow", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("vm_components_label", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("vm_trimap_fill_enclosed_workspace_bytes", c_size_t, [c_int, c_int, c_int]),
     ("vm_trimap_fill_enclosed", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -1261,22 +1261,70 @@ def trimap_from_plate_workspace_bytes(n, h, w):
     return lib().vm_trimap_from_plate_workspace_bytes(n, h, w)
 
 
+# the shadow-tolerant distance (vm_trimap_from_plate_shadow): light ratios in 1/256 and a level; a numpy prototype's
+# values, untuned on real footage
+SHADOW_DEFAULTS = {"floor": 128, "ceil": 256, "dark": 32}
+SHADOW_ONE = 256
+
+
+def check_shadow_options(who, floor=SHADOW_DEFAULTS["floor"], ceil=SHADOW_DEFAULTS["ceil"],
+                         dark=SHADOW_DEFAULTS["dark"]):
+    """The options of vm_trimap_from_plate_shadow as it checks them, on the host: integers, floor in 1..256, ceil in
+    256..512 (so floor <= ceil) and dark in 0..255 -> (floor, ceil, dark)."""
+    floor, ceil = check_int(who, "floor", floor), check_int(who, "ceil", ceil)
+    dark = check_int(who, "dark", dark, 0, 255)
+    if floor > ceil:
+        raise ValueError("%s: floor <= ceil expected, got floor %d, ceil %d" % (who, floor, ceil))
+    return check_int(who, "floor", floor, 1, SHADOW_ONE), check_int(who, "ceil", ceil, SHADOW_ONE, 2 * SHADOW_ONE), dark
+
+
+def shadow_options(who, options):
+    """A dict over SHADOW_DEFAULTS (None: the defaults), checked -> {"floor": floor, "ceil": ceil, "dark": dark}."""
+    return _options(who, SHADOW_DEFAULTS, options, check_shadow_options)
+
+
+SHADOW_CHROMA = "chroma"
+
+
+def check_shadow_mode(who, shadow, options):
+    """The ``shadow`` argument of FrameStream and reader.trimap_from_plate: None or "chroma", and their
+    ``shadow_options`` (a dict over SHADOW_DEFAULTS) only with "chroma" -> the checked options, or None without it."""
+    if shadow is not None and not (isinstance(shadow, str) and shadow == SHADOW_CHROMA):
+        raise ValueError("%s: shadow must be None or %r, got %r" % (who, SHADOW_CHROMA, shadow))
+    if shadow is None:
+        if options is not None:
+            raise ValueError("%s: shadow_options go with shadow=%r" % (who, SHADOW_CHROMA))
+        return None
+    return shadow_options("%s: shadow_options" % who, options)
+
+
 def trimap_from_plate(cmp, bg, lo=PLATE_DEFAULTS["lo"], hi=PLATE_DEFAULTS["hi"], r_bg=PLATE_DEFAULTS["r_bg"],
-                      r_fg=PLATE_DEFAULTS["r_fg"], out=None, work=None):
+                      r_fg=PLATE_DEFAULTS["r_fg"], out=None, work=None, shadow=None):
     """vm_trimap_from_plate: trimaps from the frames' difference to the background.  cmp u8 [n,h,w,3] BGR, bg u8
     [n,h,w,3] or one static plate [h,w,3] / [1,h,w,3] -> uint8 [n,h,w]: 0 where the 3x3 box sum of the squared colour
     distance stays within 9 lo^2 over a (2 r_bg + 1)^2 window, 255 where it reaches 9 hi^2 over a (2 r_fg + 1)^2 window,
     128 elsewhere (include/vmatting.h).  ``out``: a contiguous uint8 [n,h,w] device tensor; ``work``: a uint8 device
-    buffer of trimap_from_plate_workspace_bytes(n, h, w); both are allocated when None."""
+    buffer of trimap_from_plate_workspace_bytes(n, h, w); both are allocated when None.  ``shadow``: None, or a dict
+    over SHADOW_DEFAULTS for vm_trimap_from_plate_shadow: where the frame's pixel is the plate's colour under a light
+    ratio within floor / 256 .. ceil / 256, and the plate is no darker than ``dark``, the squared distance to the line
+    through the plate's colour stands for the squared distance to the plate (a per-pixel colour test: a subject that
+    is a darker version of the plate's own hue passes as shadow)."""
     who = "trimap_from_plate"
     n, h, w, nb = _check_frames_and_bg(who, cmp, bg)
     lo, hi, r_bg, r_fg = check_plate_options(who, lo, hi, r_bg, r_fg)
+    if shadow is not None:
+        shadow = shadow_options("%s: shadow" % who, shadow)
     out = _out_or_new(who, "out", out, torch.uint8, "n,h,w", cmp.device, ValueError, n=n, h=h, w=w)
     for t in (cmp, bg, out):
         _require_gpu(t)
     work = _buffer_or_new(who, "work", work, torch.uint8, trimap_from_plate_workspace_bytes(n, h, w), cmp.device)
-    check(lib().vm_trimap_from_plate(_ptr(cmp), _ptr(bg), nb, n, h, w, lo, hi, r_bg, r_fg, _ptr(out), _ptr(work),
-                                     stream_handle()), who)
+    if shadow is None:
+        check(lib().vm_trimap_from_plate(_ptr(cmp), _ptr(bg), nb, n, h, w, lo, hi, r_bg, r_fg, _ptr(out), _ptr(work),
+                                         stream_handle()), who)
+    else:
+        check(lib().vm_trimap_from_plate_shadow(_ptr(cmp), _ptr(bg), nb, n, h, w, lo, hi, r_bg, r_fg, shadow["floor"],
+                                                shadow["ceil"], shadow["dark"], _ptr(out), _ptr(work),
+                                                stream_handle()), who)
     return out
 
 

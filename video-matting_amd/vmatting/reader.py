@@ -251,13 +251,17 @@ def smooth_mattes(mattes, frames_u8, flows=None, **options):
 
 
 def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, fill=None, gain=None,
-                      gain_options=None, align=None, align_options=None):
+                      gain_options=None, align=None, align_options=None, shadow=None, shadow_options=None):
     """The trimap of a frame from its difference to the background plate: what FrameStream(trimap="auto") feeds the
     model, and the trimap of a clip's first frame for ClipStream's alpha0.  cmp_u8 uint8 BGR, one frame [H,W,3] or a
     stack [N,H,W,3]; bg_u8 uint8 [H,W,3] (one plate) or, with a stack, [N,H,W,3] -> uint8 [H,W] or [N,H,W]: 0 where the
     frame equals the plate within ``lo`` levels over a (2 r_bg + 1)^2 window, 255 where it differs by ``hi`` or more
     over a (2 r_fg + 1)^2 window, 128 elsewhere (ops.trimap_from_plate, include/vmatting.h; None: ops.PLATE_DEFAULTS,
-    which are untuned).  No shadow model, and no exposure model unless ``gain`` is "fit" (FrameStream's ``gain``): every
+    which are untuned).  No shadow model unless ``shadow`` is "chroma" (FrameStream's ``shadow``): after ``align`` and
+    ``gain``, on the plate they produce, a pixel that is the plate's colour under a light ratio a shadow may have is
+    measured by its distance to the line through that colour (``shadow_options`` over ops.SHADOW_DEFAULTS, untuned; a
+    per-pixel colour test: a subject that is a darker version of the plate's own hue passes as shadow and is labelled
+    background).  No exposure model unless ``gain`` is "fit" (FrameStream's ``gain``): every
     frame is then compared with the plate under that frame's fitted gains (match_plate; ``gain_options`` over
     ops.GAIN_DEFAULTS).  No motion model unless ``align`` is "fit" (FrameStream's ``align``): the plate is first, ahead
     of the gain, resampled through each frame's fitted affine map (align_plate; ``align_options`` over
@@ -269,6 +273,7 @@ def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, 
     cap = ops.check_fill(who, fill)
     gopts = ops.check_gain_mode(who, gain, gain_options)
     aopts = ops.check_align_mode(who, align, align_options)
+    sopts = ops.check_shadow_mode(who, shadow, shadow_options)
     if isinstance(cmp_u8, torch.Tensor) != isinstance(bg_u8, torch.Tensor):
         raise TypeError("%s: cmp and bg are both numpy arrays or both torch tensors" % who)
     given = {"lo": lo, "hi": hi, "r_bg": r_bg, "r_fg": r_fg}
@@ -289,7 +294,7 @@ def trimap_from_plate(cmp_u8, bg_u8, lo=None, hi=None, r_bg=None, r_fg=None, *, 
         bg = _aligned_plates(cmp, bg, aopts)[0]
     if gopts is not None:
         bg = ops.plate_gain_apply(bg, ops.plate_gain_fit(cmp, bg, **gopts)[0])
-    out = ops.trimap_from_plate(cmp, bg, **opts)
+    out = ops.trimap_from_plate(cmp, bg, shadow=sopts, **opts)
     if cap is not None:
         ops.trimap_fill_enclosed(out, cap, out=out)
     return _like(out, cmp_u8, single)

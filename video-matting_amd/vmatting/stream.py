@@ -20,6 +20,7 @@ the frames only, never on the model's output, so the forward stays chunked.
 
 ``trimap="auto"``: the user has no trimap at all.  The chunk's chain starts with ops.trimap_from_plate on the uploaded
 frames and the plate, followed with ``auto_fill`` by ops.trimap_fill_enclosed in place; nothing is kept between chunks.
+With ``shadow="chroma"`` that call measures a pixel that may be the plate in shadow by its chromaticity alone.
 
 ``gain="fit"``: the plate and the frames were not shot at one exposure.  The chunk's chain starts with
 ops.plate_gain_fit and ops.plate_gain_apply: one gain per frame and colour channel, and a gained copy of the plate per
@@ -134,7 +135,8 @@ class FrameStream(SlotPipeline):
     ``trimap="auto"`` (a 7-channel model): no trimap is supplied at all.  Source items are the ordinary
     ``(cmp, bg, None)`` (and new_bg last with "per_frame"), and every frame's trimap is
     ops.trimap_from_plate(cmp, bg, **auto_options) on the device: background where the frame equals the plate, foreground
-    where it clearly differs, unknown in between (include/vmatting.h; no shadow or exposure model).  ``auto_options``: a
+    where it clearly differs, unknown in between (include/vmatting.h; no exposure model, and no shadow model without
+    ``shadow``).  ``auto_options``: a
     dict over ops.PLATE_DEFAULTS (lo, hi, r_bg, r_fg).  The mattes are those of ``trimap=True`` fed with these trimaps,
     bit for bit; reader.trimap_from_plate shows them.  ``auto_fill``: True, or an integer area cap, turns every region
     of sure background that does not reach the frame's border (with a cap: and has at most that many pixels) unknown
@@ -183,6 +185,27 @@ class FrameStream(SlotPipeline):
     and will not be labelled background; the new plate of out="over" is not moved.  align=None is the stream without
     any of this, call for call.  ClipStream, VideoMatter and PlateEstimator do not take it.
 
+    ``shadow`` (None, the default, or "chroma"; only with trimap="auto"): let the automatic trimap tolerate cast
+    shadows.  A shadowed background pixel is the plate's colour scaled by a factor below 1 (Horprasert et al., 1999), so
+    where the frame's pixel has a light ratio to the background's within floor / 256 .. ceil / 256, and the
+    background's mean level is at least ``dark``, the squared distance to the line through the background's colour
+    stands for the squared distance to the background itself; everything after that in ops.trimap_from_plate is
+    unchanged (include/vmatting.h, all integer).  ``shadow_options``: a dict over ops.SHADOW_DEFAULTS (floor, ceil, dark
+    - the values of a numpy prototype, untuned on real footage).  It sees the background the rest of the chain sees:
+    aligned and gained where ``align`` and ``gain`` are on.  The mattes are those of ``trimap=True`` fed with
+    reader.trimap_from_plate(..., shadow="chroma")'s trimaps, bit for bit.  It keeps no state and works with
+    ``auto_fill``, ``scale``, ``gain``, ``align``, ``smooth`` and every ``out``.  On a synthetic scene a
+    soft shadow keeping 0.8 or 0.6 of the light has none of its core labelled background without it - at 0.6 some of
+    it sure foreground - and 0.72-0.84 with it.  What it is not: a per-pixel colour test, so a subject that is a darker
+    version of the plate's own hue passes as shadow and is labelled background (a dark-grey shirt on a light-grey wall,
+    any grey on any grey; ``auto_fill`` repairs only an enclosed one); no smoothness or texture test of the light
+    ratio and no temporal test; a shadow deeper than ``floor``, or within noise of it, falls back to the plain
+    distance, and one such pixel costs its whole (2 r_bg + 3)^2 neighbourhood (with floor 128 a 0.6 shadow holds, a
+    0.45 shadow with floor 100 mostly does not); background pixels darker than ``dark`` get no tolerance; only the
+    trimap changes - the model still sees the shadowed frame against the unshadowed plate - and out="over" carries the
+    shadow onto the new plate additively (cmp - bg), not as a multiplicative shadow pass.  shadow=None is the stream
+    without any of this, call for call.  ClipStream, VideoMatter and PlateEstimator do not take it.
+
     ``smooth`` (None, the default, or "flow"): filter the mattes along time before they are quantised or composed.
     After the forward (and, with ``scale``, the upsampling) frame j's matte is pulled towards the filtered matte of
     frame j - 1, sampled where frame j's backward flow says each pixel came from, by ``strength`` times a weight that
@@ -209,7 +232,8 @@ class FrameStream(SlotPipeline):
 
     def __init__(self, model, h, w, chunk=8, depth=2, trimap=True, static_bg=None, out="u8", graph=True, new_bg=None,
                  flow=None, flow_options=None, grow=1, auto_options=None, auto_fill=None, scale=1, guided_options=None,
-                 gain=None, gain_options=None, smooth=None, smooth_options=None, align=None, align_options=None):
+                 gain=None, gain_options=None, smooth=None, smooth_options=None, align=None, align_options=None,
+                 shadow=None, shadow_options=None):
         h, w, chunk, depth = int(h), int(w), int(chunk), int(depth)
         if h < 1 or w < 1 or chunk < 1 or depth < 1:
             raise ValueError("FrameStream: h, w, chunk and depth must be positive (got %d, %d, %d, %d)" %
@@ -239,6 +263,10 @@ class FrameStream(SlotPipeline):
         if auto_fill is not None and not self.auto:
             raise ValueError("FrameStream: auto_fill goes with trimap=%r" % AUTO)
         self.auto_fill = ops.check_fill("FrameStream: auto_fill", auto_fill)
+        # shadow="chroma": the shadow-tolerant distance's options (None: the plain distance)
+        if (shadow is not None or shadow_options is not None) and not self.auto:
+            raise ValueError("FrameStream: shadow and shadow_options go with trimap=%r" % AUTO)
+        self.shadow = ops.check_shadow_mode("FrameStream", shadow, shadow_options)
         # smooth="flow": the filter's options (None: no filter)
         self.smooth = ops.check_smooth_mode("FrameStream", smooth, smooth_options)
         if self.smooth is not None and model.split_mode == "f16x3":
@@ -553,7 +581,8 @@ class FrameStream(SlotPipeline):
         if self.propagate:
             self._trimaps(s, k, keyed)
         if self.auto:
-            ops.trimap_from_plate(s.d_cmp[:k], bg, out=s.d_tri[:k], work=self._auto_work, **self.auto_options)
+            ops.trimap_from_plate(s.d_cmp[:k], bg, out=s.d_tri[:k], work=self._auto_work, shadow=self.shadow,
+                                  **self.auto_options)
             if self.auto_fill is not None:
                 ops.trimap_fill_enclosed(s.d_tri[:k], self.auto_fill, out=s.d_tri[:k], work=self._fill_work)
         self._feed(s, k, bg)
